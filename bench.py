@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- self-play games/sec of the MI355X-native generator (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One lock-step ROUND = one MCTS simulation for every resident game: the ResNet evaluates the G leaf
@@ -125,6 +125,35 @@ def kernel_timeline(sess, stream, net, n_rounds: int = 300, batch: int = 100):
     finally:
         net.stage_hook = prev_hook
     return [(k, totals[k][0], totals[k][1]) for k in order], done, null_us
+
+
+DUMP_MAX_SAMPLES = 1 << 19   # 68 bytes per record as written: 34 MB at most (the dump may take 64 MB)
+
+
+def dump_outputs(out_dir: str, sessions, wanted) -> dict:
+    """`--dump-outputs DIR`: what the timed path hands a caller -- the sample records (c4a0_amd/session.py SAMPLE_DTYPE, what
+    play_games returns) of a fixed set of games: the first wanted[p] requests of session p, all finished.  They are merged in
+    (game id, ply) order and written field by field as DIR/<field>.npy: float64 for the integer fields (bitboards < 2^53, exact),
+    float32 for the rest.  Above DUMP_MAX_SAMPLES records a fixed, seeded subset of them is written."""
+    from c4a0_amd.session import SAMPLE_DTYPE
+
+    parts = []
+    for sp, w in zip(sessions, wanted):
+        c = sp.sample_counts()
+        recs = sp.pack_samples_device().cpu().numpy().reshape(-1).view(SAMPLE_DTYPE)   # finished games, request order
+        assert len(recs) == int(c.sum()) and (c[:w] > 0).all(), (len(recs), int(c.sum()))
+        parts.append(recs[np.repeat(np.arange(len(c)) < w, c.astype(np.int64))])
+    recs = np.concatenate(parts)
+    recs = recs[np.lexsort((recs["meta"] & 0xFFFF, recs["game_id"]))]
+    n_all = len(recs)
+    if n_all > DUMP_MAX_SAMPLES:
+        recs = recs[np.sort(np.random.default_rng(1337).choice(n_all, DUMP_MAX_SAMPLES, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for field in ("game_id", "mask", "value", "meta"):
+        np.save(os.path.join(out_dir, f"samples_{field}.npy"), recs[field].astype(np.float64))
+    for field in ("policy", "q_penalty", "q_no_penalty"):
+        np.save(os.path.join(out_dir, f"samples_{field}.npy"), np.ascontiguousarray(recs[field], dtype=np.float32))
+    return {"dir": out_dir, "games": int(sum(wanted)), "samples": n_all, "samples_written": int(len(recs))}
 
 
 def usable_cores() -> int:
@@ -604,7 +633,12 @@ def main():
     ap.add_argument("--other-configs-total-seconds", type=float, default=480.0, help="time limit of all other_configs legs TOGETHER (legs past it are skipped)")
     ap.add_argument("--whole-job-games", type=int, default=1700)
     ap.add_argument("--whole-job-n-mcts", type=int, default=1400)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the sample records of a fixed set of games (the first requests, played to the end) "
+                         "to DIR/<field>.npy (rank 0; float32 / float64, a seeded subset above %d records)" % DUMP_MAX_SAMPLES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -754,6 +788,20 @@ def main():
         sys.exit(f"device error {c1['error']} in slot {c1['error_slot']}")
     d = {k: c1[k] - c0[k] for k in c1 if k not in ("error", "error_slot")}
     elapsed = t1 - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # Slots take queued games in the order they free up, so WHICH games finish inside the timed steps varies by a few from run
+        # to run (each game's records do not).  The dump therefore holds a fixed set of games, the first K requests (K from the
+        # arguments alone: about half of what the rounds so far finish), and plays on, untimed, until every one of them has finished.
+        K = min(n_games, max(1, G * (preroll + warm_rounds + timed_rounds) // (24 * max(1, n_iter))))
+        wanted = [len(range(p, K, P)) for p in range(P)]
+        extra = 0
+        while any((sp.sample_counts()[:w] == 0).any() for sp, w in zip(sessions, wanted)):
+            if extra > 50 * 43 * (n_iter + 2):
+                sys.exit(f"--dump-outputs: the first {K} games did not finish within {extra} more rounds")
+            run_steps(64)
+            extra += 64
+        dumped = dict(dump_outputs(args.dump_outputs, sessions, wanted), rounds_after_timed_steps=extra)
 
     # ---- instrumented segment right after the timed steps (same steady state): the step kernel of
     # session 0 bracketed by HIP events on its stream, and timed on the device clock inside the
@@ -1019,6 +1067,8 @@ def main():
                    "mfma_busy_frac": mfma_busy, "mfma_busy_source": mfma_src, "hidden_layer_gemm": net.gemm,
                    "path": net.path},   # "hip" = hand-written tower + GEMM + output kernels; "torch" = PyTorch / library kernels somewhere in the chain
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if allgather is not None:
             out["sample_allgather"] = allgather
         if per_rank is not None:

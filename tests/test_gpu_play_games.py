@@ -386,7 +386,7 @@ def test_second_device_after_the_first():
     """sessions, the conv tower's LDS opt-in and the head kernel on device 1 after device 0
     in the same process; the caller's current device is left alone.  Needs two visible devices."""
     if torch.cuda.device_count() < 2:
-        pytest.skip("one visible device")
+        pytest.skip(f"needs 2 GPUs, found {torch.cuda.device_count()}")
     import c4a0_amd
     from c4a0_amd.nn import ConnectFourNet, InferenceNet, ModelConfig
 
