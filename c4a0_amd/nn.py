@@ -117,6 +117,43 @@ def pack_tower_weights(conv_w, conv_b, channels: int):
     return p0.contiguous(), pw.contiguous(), bias.contiguous()
 
 
+def pack_f32_weights(conv_w, conv_b, pol_w, pol_b, val_w, val_b, channels: int) -> dict:
+    """The (BN-folded) f32 network in the layouts of the f32 kernels (c4a0_amd/csrc/c4_f32_net.hip; the order of every sum is
+    include/c4a0_hip.h's "f32 evaluator").  C channels are padded to Cp = 16 ceil(C / 16), the heads' hidden width F = 42 C to
+    Hp = 32 ceil(F / 32); padded weights and biases are zero, so padded channels and features stay zero.
+
+      conv_w[0] [C, 2, 3, 3]  -> w0   [Cp][32]:    w0[co][2 tap + ci], tap = 3 kh + kw (zero from 18 on)
+      conv_w[1:] [C, C, 3, 3] -> w    [2 n_blocks][Cp][9 Cp]: w[co][tap Cp + ci]
+      conv_b                  -> bias [1 + 2 n_blocks][Cp]
+      heads: the first layer's input "c h w" (nn.py:111) becomes the tower's cell-major [42][Cp]; hidden layers [Hp][K],
+             output layers [7 | 2][K], K = 42 Cp for the first layer and Hp after it."""
+    c = channels
+    cp, f = -(-c // 16) * 16, 42 * c
+    hp = -(-f // 32) * 32
+    w0 = torch.zeros(cp, 32)
+    w0[:c, :18] = conv_w[0].float().reshape(c, 2, 9).permute(0, 2, 1).reshape(c, 18)
+    layers = [F.pad(w.float().reshape(c, c, 9).permute(0, 2, 1), (0, cp - c, 0, 0, 0, cp - c)).reshape(cp, 9 * cp) for w in conv_w[1:]]
+    w = torch.stack(layers) if layers else torch.zeros(0, cp, 9 * cp)
+    bias = torch.stack([F.pad(b.float(), (0, cp - c)) for b in conv_b])
+
+    def head(ws, bs):
+        out_w, out_b = [], []
+        for i, (wt, b) in enumerate(zip(ws, bs)):
+            n = wt.shape[0] if i == len(ws) - 1 else hp
+            if i == 0:
+                wt = F.pad(wt.float().reshape(-1, c, 42).permute(0, 2, 1), (0, cp - c)).reshape(-1, 42 * cp)
+            else:
+                wt = F.pad(wt.float(), (0, hp - f))
+            out_w.append(F.pad(wt, (0, 0, 0, n - wt.shape[0])).contiguous())
+            out_b.append(F.pad(b.float(), (0, n - b.shape[0])).contiguous())
+        return out_w, out_b
+
+    pw, pb = head(pol_w, pol_b)
+    vw, vb = head(val_w, val_b)
+    return {"cp": cp, "hp": hp, "w0": w0.contiguous(), "w": w.contiguous(), "bias": bias.contiguous(),
+            "pol_w": pw, "pol_b": pb, "val_w": vw, "val_b": vb}
+
+
 class EvaluatorFallbackWarning(UserWarning):
     """An InferenceNet that leaves the hand-written HIP kernels (channels not 32 / 64, or not bf16, or not on a HIP device)."""
 
@@ -125,7 +162,8 @@ class InferenceNet:
     """Device-resident evaluator: planes[G,2,6,7] -> (policy_logprobs[G,7] f32, q[G,2] f32).
 
     `hip_tower=True` (default on a HIP device in bf16 with 32 or 64 channels) runs the conv tower
-    as the hand-written MFMA kernel `c4_conv_tower_bf16`; otherwise PyTorch-ROCm convs + the library GEMM -- a path
+    as the hand-written MFMA kernel `c4_conv_tower_bf16`; with dtype=torch.float32 it selects the f32 chain instead
+    (c4_conv_tower_f32 + c4_linear_f32 + c4_head_out_f32: exact-f32 MFMA, any width 1..64, batch-invariant); otherwise PyTorch-ROCm convs + the library GEMM -- a path
     whose low bits depend on the batch (`batch_invariant` False), slower, and never the one the parity suite certifies.
     Leaving the hand-written kernels is therefore LOUD: `strict=True` refuses (ValueError), the default warns once per
     construction (EvaluatorFallbackWarning) and `path` says which one runs ("hip" | "torch"; the bench line carries it)."""
@@ -150,14 +188,21 @@ class InferenceNet:
         self.dtype = dtype
         model = model.eval()
         self.channels = model.config.conv_filter_size
-        can_tower = self.device.type == "cuda" and dtype == torch.bfloat16 and self.channels in (32, 64)
+        # f32 networks on the hand-written path only when asked for (hip_tower=True): the f32 chain has no bf16 switches
+        self.f32 = dtype == torch.float32 and bool(hip_tower)
+        if self.f32:
+            if self.device.type != "cuda" or not 1 <= self.channels <= 64:
+                raise ValueError("the f32 HIP evaluator needs a HIP device and 1 to 64 channels")
+            if gemm not in (None, "hip") or gemm_config is not None or tower_config:
+                raise ValueError("gemm / gemm_config / tower_config are bf16 switches: the f32 HIP evaluator has none")
+        can_tower = self.device.type == "cuda" and ((dtype == torch.bfloat16 and self.channels in (32, 64)) or self.f32)
         if hip_tower and not can_tower:
             raise ValueError("hip_tower needs a HIP device, bf16 and 32 or 64 channels")
         self.hip_tower = can_tower if hip_tower is None else bool(hip_tower)
         if not self.hip_tower and hip_tower is None and self.device.type == "cuda":
             # nobody asked for PyTorch's kernels (hip_tower=False does: the A/B switch of the tests): say so
             why = (f"{self.channels} channels (the HIP tower and GEMM are written for 32 and 64)" if dtype == torch.bfloat16
-                   else f"dtype {dtype} (the HIP kernels compute in bf16)")
+                   else f"dtype {dtype} (the default HIP kernels compute in bf16; f32 networks: hip_tower=True)")
             msg = (f"InferenceNet: {why}: this evaluator runs on PyTorch's convolutions and the library GEMM, not on the "
                    "hand-written HIP kernels -- slower, and a position's low bits depend on the batch it is evaluated in")
             if strict:
@@ -188,6 +233,10 @@ class InferenceNet:
 
         self.pol_w, self.pol_b = head(model.fc_policy)
         self.val_w, self.val_b = head(model.fc_value)
+        self._np_lock = threading.Lock()   # forward_numpy keeps ONE pinned slot, stream and graph set per net
+        if self.f32:
+            self._init_f32()
+            return
         if self.hip_tower:
             from . import _lib
 
@@ -217,7 +266,6 @@ class InferenceNet:
         self.gemm = gemm
         if strict and gemm != "hip":
             raise ValueError("InferenceNet(strict=True): gemm='hipblaslt' leaves the hand-written GEMM (its low bits depend on the batch)")
-        self._np_lock = threading.Lock()   # forward_numpy keeps ONE pinned slot, stream and graph set per net
         # every kernel of the evaluator computes a row from that row alone in one fixed order: a position's outputs do
         # not depend on the batch (session.narrow_if_worthwhile may then narrow whenever it likes)
         self.batch_invariant = self.hip_tower and gemm == "hip"
@@ -238,6 +286,28 @@ class InferenceNet:
             for b in self.pol_b[:-1] + self.val_b[:-1] + ([self.merged_b1] if self.merged_b1 is not None else []):
                 self._bias32[b.data_ptr()] = b.float().contiguous()
 
+    def _init_f32(self):
+        """The f32 chain: every product an exact-f32 MFMA fmaf chain in the documented order (include/c4a0_hip.h), so a row's
+        outputs depend on that row alone (batch_invariant) and equal tests/f32_net_ref.c bit for bit."""
+        from . import _lib
+
+        self._L = _lib.lib()
+        pk = pack_f32_weights(self.conv_w, self.conv_b, self.pol_w, self.pol_b, self.val_w, self.val_b, self.channels)
+        mv = lambda ts: [t.to(self.device, torch.float32).contiguous() for t in ts]
+        self.cp, self.hp = pk["cp"], pk["hp"]
+        self.tw0, self.tw, self.tbias = mv([pk["w0"], pk["w"], pk["bias"]])
+        self.conv_w, self.conv_b = [], []   # the unpacked copies are not kept on the device
+        self.pol_w, self.pol_b, self.val_w, self.val_b = mv(pk["pol_w"]), mv(pk["pol_b"]), mv(pk["val_w"]), mv(pk["val_b"])
+        self.pol_b32, self.val_b32 = self.pol_b[-1], self.val_b[-1]
+        self.merged_w1 = self.merged_b1 = None
+        if len(self.pol_w) > 1 and len(self.val_w) > 1:
+            self.merged_w1 = torch.cat([self.pol_w[0], self.val_w[0]], dim=0).contiguous()
+            self.merged_b1 = torch.cat([self.pol_b[0], self.val_b[0]], dim=0).contiguous()
+        self.hip_tower, self.gemm, self.batch_invariant = True, "hip", True
+        self.gemm_config, self.tower_config = (0, 0), 0
+        self.fused_epilogue = False
+        self._bias32 = {}
+
     @property
     def path(self) -> str:
         """Which kernels run: "hip" = the hand-written tower, GEMM and output kernels; "torch" = any PyTorch / library kernel in the chain."""
@@ -248,6 +318,20 @@ class InferenceNet:
         """Conv tower -> flattened features [G, 42*C] (cell-major when hip_tower, else "c h w").  latency: this call's
         answer to `latency_mode` (None = the attribute)."""
         latency = self.latency_mode if latency is None else latency
+        if self.f32:
+            from ._lib import check
+            import ctypes as C
+
+            x = planes if planes.dtype == torch.float32 else planes.float()
+            x = x.contiguous()
+            g = x.shape[0]
+            out = torch.empty((g, 42 * self.cp), dtype=torch.float32, device=self.device)
+            work = torch.empty_like(out) if self.n_blocks else None
+            check(self._L.c4_conv_tower_f32(C.c_void_p(x.data_ptr()), C.c_void_p(self.tw0.data_ptr()), C.c_void_p(self.tw.data_ptr()),
+                                            C.c_void_p(self.tbias.data_ptr()), g, self.cp, self.n_blocks, C.c_void_p(out.data_ptr()),
+                                            C.c_void_p(work.data_ptr() if work is not None else None),
+                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            return out
         if self.hip_tower:
             from ._lib import check
             import ctypes as C
@@ -275,7 +359,7 @@ class InferenceNet:
     @torch.no_grad()
     def forward_hidden(self, planes: torch.Tensor, latency: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Everything but the heads' output layers: planes -> (policy head's last hidden activations, value head's), bf16
-        [G, F] row views (column stride 1).  The output layers follow in `forward`, or inside the session's fused output +
+        [G, F] row views (column stride 1; f32 [G, Hp] on the f32 chain, Hp = F padded to a multiple of 32).  The output layers follow in `forward`, or inside the session's fused output +
         step launch (DeviceSession.round, c4_session_step_head_out)."""
         hook = self.stage_hook
         if hook is not None:
@@ -316,7 +400,7 @@ class InferenceNet:
         so for it the session keeps evaluate() -> step() (the same answer as setting
         DeviceSession.fuse_output_step = False)."""
         own = type(self).forward is InferenceNet.forward and type(self).__call__ is InferenceNet.__call__
-        return own and bool(self.hip_tower) and (42 * self.channels) % 1344 == 0
+        return own and bool(self.hip_tower) and self.dtype == torch.bfloat16 and (42 * self.channels) % 1344 == 0
 
     def head_out_operands(self):
         """(w_policy, w_value, b_policy f32, b_value f32) of the output layers, as the HIP output kernels take them."""
@@ -326,6 +410,8 @@ class InferenceNet:
     def forward(self, planes: torch.Tensor, out_logprobs: Optional[torch.Tensor] = None,
                 out_q: Optional[torch.Tensor] = None, latency: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         p, v = self.forward_hidden(planes, latency)
+        if self.f32:
+            return self._head_out_f32(p, v, out_logprobs, out_q)
         if self.hip_tower:
             # both output layers + log-softmax + tanh in one HIP launch, written in place
             from ._lib import check
@@ -350,6 +436,23 @@ class InferenceNet:
         q = torch.tanh(v) if out_q is None else torch.tanh(v, out=out_q)
         return lp, q
 
+    def _head_out_f32(self, p, v, out_logprobs=None, out_q=None, out_preact=None):
+        """c4_head_out_f32: both output layers, log-softmax and tanh written in place (out_preact [G, 9]: the pre-activations too)."""
+        from ._lib import check
+        import ctypes as C
+
+        g = p.shape[0]
+        lp = out_logprobs if out_logprobs is not None else torch.empty((g, 7), dtype=torch.float32, device=self.device)
+        q = out_q if out_q is not None else torch.empty((g, 2), dtype=torch.float32, device=self.device)
+        assert p.stride(1) == 1 and v.stride(1) == 1
+        check(self._L.c4_head_out_f32(C.c_void_p(p.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(self.pol_w[-1].data_ptr()),
+                                      C.c_void_p(self.val_w[-1].data_ptr()), C.c_void_p(self.pol_b32.data_ptr()), C.c_void_p(self.val_b32.data_ptr()),
+                                      g, self.pol_w[-1].shape[1], self.val_w[-1].shape[1], p.stride(0), v.stride(0),
+                                      C.c_void_p(lp.data_ptr()), C.c_void_p(q.data_ptr()),
+                                      C.c_void_p(out_preact.data_ptr() if out_preact is not None else None),
+                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        return lp, q
+
     # ---------------------------------------------------------------- the reference's numpy entry point
     _NP_BUCKET = 128
 
@@ -363,7 +466,8 @@ class InferenceNet:
         The reference's version is a host round trip around ~35 eager launches.  Here ONE HIP-graph replay and one stream
         synchronisation: the graph (captured once per batch size rounded up to a multiple of 128 rows: the kernels compute a
         row from that row alone, so padding rows change nothing) is c4_planes_from_f32 + tower + GEMMs + output kernel, and
-        the output kernel writes into pinned host memory itself.  A batch that already lives in pinned host memory -- what
+        the output kernel writes into pinned host memory itself.  The f32 network (hip_tower=True) reads f32 positions as they
+        are: the batch is copied into the graph's device input (no conversion kernel), then the same one replay.  A batch that already lives in pinned host memory -- what
         `play_games` hands its callback -- is read by the first kernel over PCIe where it is (its address travels in a
         pinned word, c4_f32_batch); any other array takes one copy into a device buffer first."""
         import ctypes as C
@@ -399,7 +503,7 @@ class InferenceNet:
             cap = max(2048, 1 << (bucket - 1).bit_length())
             st = self._np = {"cap": cap, "graphs": {}, "stream": torch.cuda.Stream(device=self.device),
                              "in": torch.zeros((cap, 2, 6, 7), dtype=torch.float32, device=self.device),
-                             "planes": torch.zeros((cap, 2, 6, 7), dtype=torch.bfloat16, device=self.device),
+                             "planes": None if self.f32 else torch.zeros((cap, 2, 6, 7), dtype=torch.bfloat16, device=self.device),
                              "slot": torch.zeros(2, dtype=torch.int64).pin_memory(),      # c4_f32_batch {data, n_boards}
                              "h_lp": torch.zeros((cap, 7), dtype=torch.float32).pin_memory(),
                              "h_q": torch.zeros((cap, 2), dtype=torch.float32).pin_memory()}
@@ -413,6 +517,9 @@ class InferenceNet:
                 from .session import CAPTURE_ERROR_MODE
 
                 def body():
+                    if self.f32:     # the f32 chain reads the f32 positions themselves (rows b .. bucket - 1: earlier batches, unread)
+                        self.forward(st["in"][:bucket], out_logprobs=st["h_lp"][:bucket], out_q=st["h_q"][:bucket], latency=True)
+                        return
                     check(self._L.c4_planes_from_f32(C.c_void_p(st["slot"].data_ptr()), None, 0, C.c_void_p(st["planes"].data_ptr()), bucket,
                                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
                     # the output kernel's stores go to pinned host memory: no copy after it.  latency=True: a host round
@@ -427,7 +534,9 @@ class InferenceNet:
                 with torch.cuda.graph(g, stream=stream, capture_error_mode=CAPTURE_ERROR_MODE):
                     body()
                 st["graphs"][bucket] = g
-            if direct:
+            if self.f32:
+                st["in"][:b].copy_(xt if xt is not None else torch.from_numpy(x.copy()), non_blocking=True)
+            elif direct:
                 st["slot_np"][0] = x.ctypes.data
             else:
                 st["in"][:b].copy_(torch.from_numpy(x), non_blocking=True)
@@ -480,6 +589,16 @@ class InferenceNet:
                      latency: Optional[bool] = None) -> torch.Tensor:
         """ReLU(x W^T + b): the hand-written MFMA GEMM, or (gemm="hipblaslt") the library's with the bias
         and ReLU in its epilogue where available."""
+        if self.f32:
+            from ._lib import check
+            import ctypes as C
+
+            assert x.stride(1) == 1 and w.is_contiguous()
+            m, n, k = x.shape[0], w.shape[0], w.shape[1]
+            y = out if out is not None else torch.empty((m, n), dtype=torch.float32, device=self.device)
+            check(self._L.c4_linear_f32(C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(y.data_ptr()),
+                                        m, n, k, x.stride(0), y.stride(0), 1, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            return y
         if self.gemm == "hip":
             from ._lib import check
             import ctypes as C

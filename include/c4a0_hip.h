@@ -24,10 +24,10 @@ extern "C" {
 #endif
 
 /* Version of THIS interface: bumped whenever a signature or a struct layout below changes (version 3 added `config` in the
- * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED).  A consumer compiled against this header checks it once at start-up --
+ * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED, version 11 the f32 evaluator c4_conv_tower_f32 / c4_linear_f32 / c4_head_out_f32).  A consumer compiled against this header checks it once at start-up --
  * `if (c4_abi_version() != C4_ABI_VERSION) refuse` -- because the dynamic linker compares names, not signatures
  * (tests/abi_consumer*.c and c4a0_amd/_lib.py do).  No reference counterpart: the reference's boundary is PyO3. */
-#define C4_ABI_VERSION 10
+#define C4_ABI_VERSION 11
 
 #define C4_N_COLS 7          /* rust/src/c4r.rs:45, lib.rs:28 */
 #define C4_N_ROWS 6          /* rust/src/c4r.rs:44, lib.rs:29 */
@@ -474,6 +474,43 @@ int c4_head_out_bf16(const void* hidden_policy_dev, const void* hidden_value_dev
                      const void* w_value_dev, const float* b_policy_dev, const float* b_value_dev,
                      uint32_t n_boards, uint32_t features, uint32_t policy_row_stride, uint32_t value_row_stride,
                      float* logprobs_dev, float* q_dev, void* stream);
+
+/* ---- f32 evaluator (ABI 11): ConnectFourNet in f32 (the reference trains and evaluates in f32, nn.py:119-130) on gfx950's exact-f32
+ * MFMA (v_mfma_f32_16x16x4_f32), for any width C = 1..64 (padded to Cp = 16 ceil(C / 16)), any number of residual blocks and any head
+ * depth.  No bf16 anywhere: f32 planes, weights, activations, accumulation.  c4a0_amd/nn.py::pack_f32_weights packs the weights.
+ *
+ * Summation order (the contract: a row's outputs depend on that row and the weights only -- never on n_boards, the row's position, the
+ * launch shape or timing).  Every matrix product is y[m][n] = act(s), s = chain(m, n) + bias[n] (one f32 add), where chain is ONE f32
+ * fmaf chain started at +0.0f over the K inputs of the product (K a multiple of 16) visited in blocks of 16, inside a block in the
+ * order k = kb + 4 h + j for j = 0..3, h = 0..3 (outer j):
+ *     acc = 0.0f;  for kb in 0, 16, .., K - 16:  for j in 0..3:  for h in 0..3:  acc = fmaf(W[n][kb + 4h + j], X[m][kb + 4h + j], acc)
+ * Zero-padded inputs and weights are part of the chain (they add +-0 products).  The K inputs of each product:
+ *   conv0      X[(g, cell)][k], k = 2 tap + ci for k < 18 (tap = 3 (dr + 1) + (dc + 1), ci = input plane), 0 for k = 18..31: the plane
+ *              value at the neighbour cell, 0 off the board; W = w0 [Cp][32]; act = none
+ *   conv       X[(g, cell)][k], k = tap Cp + ci (K = 9 Cp): channel ci of the neighbour cell of the cell-major features, 0 off the board;
+ *              W = [Cp][9 Cp]; the first conv of a block act = none, the second (BN folded) y = x + relu(s) (x = the block's input)
+ *   linear     X = the layer's input row; act = relu(s) = (s > 0 ? s : 0) for hidden layers
+ *   head out   policy v[0..6] = s, value v[7..8] = s (no activation), then logp[o] = v[o] - lse with mx = fmaxf over v[0..6] left to
+ *              right, sum = ((0 + e0) + e1) + .. + e6, e_o = c4_expf(v[o] - mx) (glibc expf), lse = mx + c4_logf(sum) (glibc logf);
+ *              q[i] = tanhf(v[7 + i]) (device libm) */
+
+/* The tower (nn.py:64-70, 184-195): planes_dev f32 [n_boards][2][6][7] -> out_dev f32 [n_boards][42][channels] (cell-major, the padded
+ * channels are 0).  channels = Cp (16, 32, 48 or 64); w0_dev [Cp][32], w_dev [2 n_blocks][Cp][9 Cp], bias_dev [1 + 2 n_blocks][Cp];
+ * work_dev: a second buffer the size of out_dev (may be NULL when n_blocks = 0).  1 + 2 n_blocks launches on `stream`.
+ * Arrays 16-byte aligned. */
+int c4_conv_tower_f32(const float* planes_dev, const float* w0_dev, const float* w_dev, const float* bias_dev, uint32_t n_boards,
+                      uint32_t channels, uint32_t n_blocks, float* out_dev, float* work_dev, void* stream);
+/* A layer of a head: y[m][n] = act(chain + bias[n]), x f32 [m][ldx] (a strided row view is fine), w f32 [n][k], bias f32 [n], y f32
+ * [m][ldy]; relu != 0: act = relu.  n % 32 == 0, k % 16 == 0, ldx and ldy multiples of 4, arrays 16-byte aligned. */
+int c4_linear_f32(const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, uint32_t m, uint32_t n, uint32_t k,
+                  uint32_t ldx, uint32_t ldy, uint32_t relu, void* stream);
+/* Output layers of both heads (nn.py:84-85, 98-99): hidden_policy [n_boards][policy_row_stride] x w_policy [7][policy_features],
+ * hidden_value [n_boards][value_row_stride] x w_value [2][value_features] -> logprobs [n_boards][7] (log-softmax) and q [n_boards][2]
+ * (tanh); preact (may be NULL) [n_boards][9] receives v (7 policy logits, 2 value pre-activations).  The outputs may be pinned host
+ * memory.  features multiples of 16, row strides multiples of 4, hidden rows and weights 16-byte aligned. */
+int c4_head_out_f32(const float* hidden_policy_dev, const float* hidden_value_dev, const float* w_policy_dev, const float* w_value_dev,
+                    const float* b_policy_dev, const float* b_value_dev, uint32_t n_boards, uint32_t policy_features, uint32_t value_features,
+                    uint32_t policy_row_stride, uint32_t value_row_stride, float* logprobs, float* q, float* preact, void* stream);
 
 #ifdef __cplusplus
 }
