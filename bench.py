@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- self-play games/sec of the MI355X-native generator (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One lock-step ROUND = one MCTS simulation for every resident game: the ResNet evaluates the G leaf
@@ -19,10 +19,13 @@ config 3 is exactly this at N = 8).  Synthetic data: empty-board starts, random-
 games have been replaced at least once, so the timed steps see the steady-state mix of game
 phases; `value` counts games COMPLETED inside the timed steps.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (fused tree step kernel vs HBM, always
->= 300 event-bracketed launches), "cpu_baseline" (the CPU oracle in the reference's thread topology
--- one evaluator thread + workers, two queues -- timed on this box's host cores), "nn" (evaluator
-FLOP rate), and for N > 1 "sample_allgather" (the path's one exchange step, merged and checked).
+Prints ONE JSON line (rank 0).  A plain run sets up, pre-rolls, warms up, times the steps, writes
+--dump-outputs if asked and prints the line: the headline, "nn" (evaluator FLOP rate over the timed
+steps) and nothing that needs a run of its own.  With --full it also measures and checks the rest:
+"roofline" (fused tree step kernel vs HBM, always >= 300 event-bracketed launches after the timed
+steps), "cpu_baseline" (the CPU oracle in the reference's thread topology -- one evaluator thread +
+workers, two queues -- timed on the host cores), "other_configs" (the other single-GPU shapes,
+N = 1), and for N > 1 "sample_allgather" (the path's one exchange step, merged and checked).
 """
 from __future__ import annotations
 
@@ -462,7 +465,7 @@ def other_config_legs(args, sessions) -> dict:
     for sp in sessions:          # the children want the HBM (config 5's trees: 2 x 4 096 slots x 8 608 blocks x 128 B = 9 GB)
         sp.close()
     torch.cuda.empty_cache()
-    base = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-other-configs"]
+    base = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-other-configs"]   # --full: the rows below read "roofline"
     legs = {
         "config4": base + ["--blocks", "8", "--channels", "64", "--n-mcts", "800", "--games-per-gpu", "4096", "--steps", "3", "--warmup", "1"],
         "config5_per_gpu": base + ["--blocks", "8", "--channels", "64", "--n-mcts", "200", "--games-per-gpu", "8192", "--steps", "3", "--warmup", "1"],
@@ -593,13 +596,16 @@ def main():
     ap.add_argument("--blocks", type=int, default=4, help="residual blocks")
     ap.add_argument("--channels", type=int, default=32)
     ap.add_argument("--preroll", type=int, default=-1, help="untimed steps to reach steady state (-1 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: the roofline and per-kernel figures (runs of their own after "
+                         "the timed steps), the CPU baseline and the other single-GPU shapes (N = 1), the sample exchange (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline object")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0)
     ap.add_argument("--eager", action="store_true", help="no HIP graph: launch every kernel from the host")
     ap.add_argument("--steps-per-graph", type=int, default=64, help="lock-step rounds per HIP-graph replay (paired graph, round 3: 16 -> 24.8 k, 32 -> 25.2 k, 64 -> 25.5 k games/s)")
     ap.add_argument("--one-sim-per-step", action="store_true",
                     help="A/B knob: C4_FLAG_ONE_SIM_PER_STEP (no same-launch simulation for terminal leaves)")
-    ap.add_argument("--instrumented-steps", type=int, default=320, help="event-bracketed step-kernel launches for the roofline object (>= 300 whatever --steps is)")
+    ap.add_argument("--instrumented-steps", type=int, default=320, help="with --full: event-bracketed step-kernel launches for the roofline object (>= 300 whatever --steps is)")
     ap.add_argument("--eval-cache", type=int, default=0,
                     help="EXTENSION, off by default and NOT part of the headline: evaluation-cache entries per session "
                          "(c4_session_set_eval_cache); repeated positions then skip the evaluator")
@@ -628,7 +634,7 @@ def main():
                     help="instead of the steady-state bench: the reference's default self-play job, whole, in callback and device modes (own JSON line)")
     ap.add_argument("--whole-job-modes", default="", help="comma-separated subset of the --whole-job modes (default: all; device_mode first: the others are compared with it)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short legs for the other single-GPU shapes (BASELINE config 4, config 5's per-GPU share, the reference's default job) that the default N = 1 run attaches as `other_configs`")
+                    help="with --full: skip the short legs for the other single-GPU shapes (BASELINE config 4, config 5's per-GPU share, the reference's default job) that an N = 1 run attaches as `other_configs`")
     ap.add_argument("--other-configs-seconds", type=float, default=150.0, help="time limit of EACH other_configs leg (a child process)")
     ap.add_argument("--other-configs-total-seconds", type=float, default=480.0, help="time limit of all other_configs legs TOGETHER (legs past it are skipped)")
     ap.add_argument("--whole-job-games", type=int, default=1700)
@@ -803,46 +809,48 @@ def main():
             extra += 64
         dumped = dict(dump_outputs(args.dump_outputs, sessions, wanted), rounds_after_timed_steps=extra)
 
-    # ---- instrumented segment right after the timed steps (same steady state): the step kernel of
-    # session 0 bracketed by HIP events on its stream, and timed on the device clock inside the
-    # kernel; the other sessions wait.  (Inside the graph-replayed region nothing can be bracketed
-    # per launch.)
-    n_inst = max(300, args.instrumented_steps)
-    sess, st0 = sessions[0], streams[0]
-    sess.set_timing(True)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_inst)]
-    ci0 = sess.counters()
-    with torch.cuda.stream(st0):
-        for a_ev, b_ev in ev:
-            sess.evaluate(net)
-            a_ev.record(st0)
-            sess.step()
-            b_ev.record(st0)
-    torch.cuda.synchronize()
-    ci1 = sess.counters()
-    if ci1["error"]:
-        sys.exit(f"device error {ci1['error']} in slot {ci1['error_slot']}")
-    di = {k: ci1[k] - ci0[k] for k in ci1 if k not in ("error", "error_slot")}
-    step_kernel_ms = sum(a_ev.elapsed_time(b_ev) for a_ev, b_ev in ev)
-    # ---- ... and the round AS THE TIMED REGION LAUNCHES IT (per-launch timing off: the heads' output layers and the step are one
-    # launch, c4_out_step_kernel), every launch of session 0 bracketed by HIP events on its stream
-    timeline, tl_rounds, dt_tl, null_us = None, 0, None, None
-    if net.path == "hip" and not args.eager and not args.no_fused_step and not args.eval_cache and not args.dirichlet and rank == 0:
-        ct0 = sess.counters()
-        timeline, tl_rounds, null_us = kernel_timeline(sess, st0, net, n_rounds=max(300, args.instrumented_steps))
-        ct1 = sess.counters()
-        if ct1["error"]:
-            sys.exit(f"device error {ct1['error']} in slot {ct1['error_slot']}")
-        dt_tl = {k: ct1[k] - ct0[k] for k in ct1 if k not in ("error", "error_slot")}
+    # ---- --full only: what the roofline and per-kernel figures need, runs of their own after the timed steps
+    if args.full:
+        # ---- instrumented segment right after the timed steps (same steady state): the step kernel of
+        # session 0 bracketed by HIP events on its stream, and timed on the device clock inside the
+        # kernel; the other sessions wait.  (Inside the graph-replayed region nothing can be bracketed
+        # per launch.)
+        n_inst = max(300, args.instrumented_steps)
+        sess, st0 = sessions[0], streams[0]
+        sess.set_timing(True)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_inst)]
+        ci0 = sess.counters()
+        with torch.cuda.stream(st0):
+            for a_ev, b_ev in ev:
+                sess.evaluate(net)
+                a_ev.record(st0)
+                sess.step()
+                b_ev.record(st0)
+        torch.cuda.synchronize()
+        ci1 = sess.counters()
+        if ci1["error"]:
+            sys.exit(f"device error {ci1['error']} in slot {ci1['error_slot']}")
+        di = {k: ci1[k] - ci0[k] for k in ci1 if k not in ("error", "error_slot")}
+        step_kernel_ms = sum(a_ev.elapsed_time(b_ev) for a_ev, b_ev in ev)
+        # ---- ... and the round AS THE TIMED REGION LAUNCHES IT (per-launch timing off: the heads' output layers and the step are one
+        # launch, c4_out_step_kernel), every launch of session 0 bracketed by HIP events on its stream
+        timeline, tl_rounds, dt_tl, null_us = None, 0, None, None
+        if net.path == "hip" and not args.eager and not args.no_fused_step and not args.eval_cache and not args.dirichlet and rank == 0:
+            ct0 = sess.counters()
+            timeline, tl_rounds, null_us = kernel_timeline(sess, st0, net, n_rounds=max(300, args.instrumented_steps))
+            ct1 = sess.counters()
+            if ct1["error"]:
+                sys.exit(f"device error {ct1['error']} in slot {ct1['error_slot']}")
+            dt_tl = {k: ct1[k] - ct0[k] for k in ct1 if k not in ("error", "error_slot")}
     if any(sp.counters()["games_started"] >= sp.n_games for sp in sessions):
         sys.exit("bench ran out of queued games; raise n_games")
 
-    # ---- multi-GPU: the one exchange step of the path -- all-gather the finished samples (untimed
+    # ---- multi-GPU, --full only: the one exchange step of the path -- all-gather the finished samples (untimed
     # end-of-job step; its time is reported beside the throughput).  Exactly what
     # c4a0_amd.distributed.play_games_sharded runs: pack on the device, counts + padded records
     # all-gathered, shards merged into request order -- and the merged result is checked.
     allgather = None
-    if dist is not None:
+    if dist is not None and args.full:
         try:
             from c4a0_amd.api import merge_parts
             from c4a0_amd.distributed import gather_shards, merge_shards
@@ -886,111 +894,147 @@ def main():
         skipped = float(d["ref_skipped_sims"])
 
     if rank == 0:
-        ab = algorithmic_bytes(di, 2)
-        avg_kernel_s = step_kernel_ms / 1e3 / n_inst                       # HIP events around each launch
-        achieved = ab["total"] / n_inst / avg_kernel_s / 1e9
-        # the same launches on the device clock (first wavefront start -> last wavefront end,
-        # s_memrealtime stamps taken inside the kernel): what rocprofv3's kernel duration measures
-        dev_s = di["step_kernel_ns"] / 1e9 / max(1, di["step_launches"])
-        achieved_dev = ab["total"] / n_inst / max(dev_s, 1e-12) / 1e9
-        traffic, traffic_current, traffic_fused = None, None, None
-        tpath = os.path.join(ROOT, "profiles", "step_kernel_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_fused = (tj.get("c4_out_step_kernel") or {}).get("hbm_bytes_per_launch")
-                # counters are collected in their own rocprofv3 --pmc passes (tools/profile/run_r06.sh), not in this run: say whether
-                # they were taken on the step kernel this library holds (hash of c4_session.hip + c4_device.hpp at collection time)
-                traffic_current = tj.get("step_kernel_source_hash") == step_kernel_source_hash()
-            except Exception:
-                traffic = None
         fl = flops_per_leaf(cfg)
-        mfma_busy, mfma_src = None, None   # counters under the evaluator: not re-measured here, read from the committed PMC summary
-        try:
-            pmc_file = next(f for f in ("r06_evaluator_pmc.json", "r05_evaluator_pmc.json", "r04_evaluator_pmc.json", "r03_evaluator_pmc.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
-            pm = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
-            mfma_busy = pm["backends"]["hip0" if net.gemm == "hip" else "hipblaslt0"]["evaluator_mfma_busy_frac_of_chip_time_weighted"]
-            mfma_src = (f"profiles/{pmc_file}: SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x launch cycles), time-weighted over the tower, the three "
-                        "hidden-layer GEMMs and the output kernel, each launch ALONE on the chip at 2 048 rows (rocprofv3 --pmc serialises kernels); "
-                        "not re-measured in this run")
-        except Exception:
-            pass
-        # ---- the fused launch of the timed region and the evaluator's kernels, from the event-bracketed rounds above
-        rows = sess.rows
-        F = 42 * cfg.conv_filter_size
-        conv_flops = 2 * 42 * 9 * 2 * cfg.conv_filter_size + cfg.n_residual_blocks * 2 * (2 * 42 * 9 * cfg.conv_filter_size ** 2)
-        kernels, fused = {}, None
-        if timeline:
-            flops = {"tower": rows * conv_flops, "gemm_first_hidden": 2 * rows * F * 2 * F, "gemm_narrow": 2 * rows * F * F}
-            names = {"tower": "c4_conv_tower_kernel", "gemm_first_hidden": "c4_head_gemm_kernel (the merged 2F-wide first hidden layer of both heads)",
-                     "gemm_narrow": "c4_head_gemm_kernel (an F-wide hidden layer)", "out_step": "c4_out_step_kernel"}
-            ab_tl = algorithmic_bytes(dt_tl, 2)
-            for label, ms, launches in timeline:
-                us = ms * 1e3 / launches
-                k = {"kernel": names[label], "calls_per_round": launches / tl_rounds, "avg_us": us, "launches_measured": launches}
-                if label in flops:
-                    tf = flops[label] / (us * 1e-6) / 1e12
-                    k.update({"bound": "mfma", "flops_per_launch": flops[label], "achieved_tflops": tf, "frac_of_mfma_peak": tf / MFMA_BF16_PEAK_TFLOPS})
-                else:
-                    gbps = ab_tl["total"] / tl_rounds / (us * 1e-6) / 1e9
-                    k.update({"bound": "hbm", "algorithmic_bytes_per_launch": ab_tl["total"] / tl_rounds, "achieved_gbps": gbps, "frac_of_hbm_peak": gbps / HBM_PEAK_GBPS})
-                    fused = k
-                kernels[label] = k
-            # the committed rocprofv3 --kernel-trace --stats summary of THIS command (tools/profile/run_r06.sh): per-kernel durations without the
-            # dispatch gap; one c4_head_gemm_kernel instance serves both layer widths at this size, so its average pools three launches
-            rocprof = {}
+        mfma_busy, mfma_src, roofline = None, None, None
+        if args.full:
+            ab = algorithmic_bytes(di, 2)
+            avg_kernel_s = step_kernel_ms / 1e3 / n_inst                       # HIP events around each launch
+            achieved = ab["total"] / n_inst / avg_kernel_s / 1e9
+            # the same launches on the device clock (first wavefront start -> last wavefront end,
+            # s_memrealtime stamps taken inside the kernel): what rocprofv3's kernel duration measures
+            dev_s = di["step_kernel_ns"] / 1e9 / max(1, di["step_launches"])
+            achieved_dev = ab["total"] / n_inst / max(dev_s, 1e-12) / 1e9
+            traffic, traffic_current, traffic_fused = None, None, None
+            tpath = os.path.join(ROOT, "profiles", "step_kernel_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    traffic_fused = (tj.get("c4_out_step_kernel") or {}).get("hbm_bytes_per_launch")
+                    # counters are collected in their own rocprofv3 --pmc passes (tools/profile/run_r06.sh), not in this run: say whether
+                    # they were taken on the step kernel this library holds (hash of c4_session.hip + c4_device.hpp at collection time)
+                    traffic_current = tj.get("step_kernel_source_hash") == step_kernel_source_hash()
+                except Exception:
+                    traffic = None
+            # counters under the evaluator: not re-measured here, read from the committed PMC summary
             try:
-                import csv
-                stats_file = next(f for f in ("r06_kernel_stats.csv", "r05_kernel_stats.csv") if os.path.exists(os.path.join(ROOT, "profiles", f)))
-                for row in csv.DictReader(open(os.path.join(ROOT, "profiles", stats_file))):
-                    for key, sub in (("tower", "c4_conv_tower_kernel"), ("out_step", "c4_out_step_kernel"), ("gemm_pooled", "c4_head_gemm_kernel")):
-                        if sub in row["Name"] and key not in rocprof:
-                            rocprof[key] = float(row["AverageNs"]) / 1e3
-                for key in ("tower", "out_step"):
-                    if key in kernels and key in rocprof:
-                        kernels[key]["rocprof_avg_us"] = rocprof[key]
-                if "gemm_pooled" in rocprof and "gemm_first_hidden" in kernels and "gemm_narrow" in kernels:
-                    g1, g2 = kernels["gemm_first_hidden"], kernels["gemm_narrow"]
-                    n_l = g1["launches_measured"] + g2["launches_measured"]
-                    fl_pooled = (g1["flops_per_launch"] * g1["launches_measured"] + g2["flops_per_launch"] * g2["launches_measured"]) / n_l
-                    us = (g1["avg_us"] * g1["launches_measured"] + g2["avg_us"] * g2["launches_measured"]) / n_l
-                    kernels["gemm_pooled"] = {"kernel": "c4_head_gemm_kernel, all three hidden-layer launches of a round pooled (as rocprofv3 names them: one instance)",
-                                              "calls_per_round": n_l / tl_rounds, "avg_us": us, "rocprof_avg_us": rocprof["gemm_pooled"], "flops_per_launch": fl_pooled,
-                                              "frac_of_mfma_peak": fl_pooled / (us * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-                                              "rocprof_frac_of_mfma_peak": fl_pooled / (rocprof["gemm_pooled"] * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS}
-                if "tower" in kernels and "rocprof_avg_us" in kernels["tower"]:
-                    kernels["tower"]["rocprof_frac_of_mfma_peak"] = kernels["tower"]["flops_per_launch"] / (kernels["tower"]["rocprof_avg_us"] * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS
-                if fused and "rocprof_avg_us" in fused:
-                    fused["rocprof_frac_of_hbm_peak"] = fused["algorithmic_bytes_per_launch"] / (fused["rocprof_avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
-                kernels["rocprof_source"] = f"profiles/{stats_file} (rocprofv3 --kernel-trace --stats of this command; not re-measured in this run)"
+                pmc_file = next(f for f in ("r06_evaluator_pmc.json", "r05_evaluator_pmc.json", "r04_evaluator_pmc.json", "r03_evaluator_pmc.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
+                pm = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
+                mfma_busy = pm["backends"]["hip0" if net.gemm == "hip" else "hipblaslt0"]["evaluator_mfma_busy_frac_of_chip_time_weighted"]
+                mfma_src = (f"profiles/{pmc_file}: SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x launch cycles), time-weighted over the tower, the three "
+                            "hidden-layer GEMMs and the output kernel, each launch ALONE on the chip at 2 048 rows (rocprofv3 --pmc serialises kernels); "
+                            "not re-measured in this run")
             except Exception:
                 pass
-            kernels["one_element_kernel_interval_us"] = null_us
-            per_round_us = sum(ms for _l, ms, _n in timeline) * 1e3 / tl_rounds
-            kernels["sum_per_session_round_us"] = per_round_us
-            kernels["share_of_round"] = {label: ms * 1e3 / tl_rounds / per_round_us for label, ms, _n in timeline}
-            kernels["rows_per_launch"] = rows
-            kernels["method"] = (f"{tl_rounds} eager rounds of one session ({rows} rows) right after the timed region, a HIP event on its stream at every launch boundary, queued in batches "
-                                 "behind a blocker so that the GPU runs them back to back; the other session idle (rocprofv3's kernel trace serialises the two queues the same way: "
-                                 "profiles/r06_kernel_stats.csv holds its averages for the same kernels: rocprof_avg_us); an event-to-event interval is the kernel PLUS the dispatch of a dependent launch -- the same "
-                                 "bracket around a chain of one-element kernels gives one_element_kernel_interval_us -- which is why avg_us exceeds rocprof_avg_us by 2.5-3.5 us")
-        issue = None   # the step kernel's issue-slot occupancy, from the committed counter summary (own rocprofv3 --pmc passes, tools/profile/run_r06.sh)
-        try:
-            pmc_step = next(f for f in ("r06_step_kernel_pmc.json", "r05_step_kernel_pmc.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
-            pw = json.load(open(os.path.join(ROOT, "profiles", pmc_step)))["games_65536"]["per_wave"]
-            waves_per_simd = 4   # 127-128 VGPRs: four wavefronts share a SIMD
-            issue = {"issue_slots_taken": pw["SQ_ACTIVE_INST_ANY_per_wave"] * waves_per_simd / pw["SQ_WAVE_CYCLES_per_wave"],
-                     "valu_share_of_issue": pw["SQ_ACTIVE_INST_VALU_per_wave"] / pw["SQ_ACTIVE_INST_ANY_per_wave"],
-                     "valu_pipe_busy": pw["SQ_ACTIVE_INST_VALU_per_wave"] * waves_per_simd / pw["SQ_WAVE_CYCLES_per_wave"],
-                     "insts_per_wavefront": {k: pw[f"SQ_INSTS_{k}_per_wave"] for k in ("VALU", "SALU", "LDS", "VMEM_RD", "VMEM_WR")},
-                     "waves_per_simd": waves_per_simd, "at_games_per_launch": 65536,
-                     "formula": "issue_slots_taken = SQ_ACTIVE_INST_ANY x wavefronts per SIMD / SQ_WAVE_CYCLES (both in quad-cycles per wavefront): the share of a SIMD's cycles in which one of its "
-                                "wavefronts issues (an upper bound on the issue stage's load: different instruction types of different wavefronts can issue together); valu_pipe_busy = the same "
-                                "with SQ_ACTIVE_INST_VALU: the vector ALU's own occupancy",
-                     "source": f"profiles/{pmc_step} (rocprofv3 --pmc, own passes; stand-alone c4_step_kernel = the step_body the fused launch runs); not re-measured in this run"}
-        except Exception:
-            pass
+            # ---- the fused launch of the timed region and the evaluator's kernels, from the event-bracketed rounds above
+            rows = sess.rows
+            F = 42 * cfg.conv_filter_size
+            conv_flops = 2 * 42 * 9 * 2 * cfg.conv_filter_size + cfg.n_residual_blocks * 2 * (2 * 42 * 9 * cfg.conv_filter_size ** 2)
+            kernels, fused = {}, None
+            if timeline:
+                flops = {"tower": rows * conv_flops, "gemm_first_hidden": 2 * rows * F * 2 * F, "gemm_narrow": 2 * rows * F * F}
+                names = {"tower": "c4_conv_tower_kernel", "gemm_first_hidden": "c4_head_gemm_kernel (the merged 2F-wide first hidden layer of both heads)",
+                         "gemm_narrow": "c4_head_gemm_kernel (an F-wide hidden layer)", "out_step": "c4_out_step_kernel"}
+                ab_tl = algorithmic_bytes(dt_tl, 2)
+                for label, ms, launches in timeline:
+                    us = ms * 1e3 / launches
+                    k = {"kernel": names[label], "calls_per_round": launches / tl_rounds, "avg_us": us, "launches_measured": launches}
+                    if label in flops:
+                        tf = flops[label] / (us * 1e-6) / 1e12
+                        k.update({"bound": "mfma", "flops_per_launch": flops[label], "achieved_tflops": tf, "frac_of_mfma_peak": tf / MFMA_BF16_PEAK_TFLOPS})
+                    else:
+                        gbps = ab_tl["total"] / tl_rounds / (us * 1e-6) / 1e9
+                        k.update({"bound": "hbm", "algorithmic_bytes_per_launch": ab_tl["total"] / tl_rounds, "achieved_gbps": gbps, "frac_of_hbm_peak": gbps / HBM_PEAK_GBPS})
+                        fused = k
+                    kernels[label] = k
+                # the committed rocprofv3 --kernel-trace --stats summary of THIS command (tools/profile/run_r06.sh): per-kernel durations without the
+                # dispatch gap; one c4_head_gemm_kernel instance serves both layer widths at this size, so its average pools three launches
+                rocprof = {}
+                try:
+                    import csv
+                    stats_file = next(f for f in ("r06_kernel_stats.csv", "r05_kernel_stats.csv") if os.path.exists(os.path.join(ROOT, "profiles", f)))
+                    for row in csv.DictReader(open(os.path.join(ROOT, "profiles", stats_file))):
+                        for key, sub in (("tower", "c4_conv_tower_kernel"), ("out_step", "c4_out_step_kernel"), ("gemm_pooled", "c4_head_gemm_kernel")):
+                            if sub in row["Name"] and key not in rocprof:
+                                rocprof[key] = float(row["AverageNs"]) / 1e3
+                    for key in ("tower", "out_step"):
+                        if key in kernels and key in rocprof:
+                            kernels[key]["rocprof_avg_us"] = rocprof[key]
+                    if "gemm_pooled" in rocprof and "gemm_first_hidden" in kernels and "gemm_narrow" in kernels:
+                        g1, g2 = kernels["gemm_first_hidden"], kernels["gemm_narrow"]
+                        n_l = g1["launches_measured"] + g2["launches_measured"]
+                        fl_pooled = (g1["flops_per_launch"] * g1["launches_measured"] + g2["flops_per_launch"] * g2["launches_measured"]) / n_l
+                        us = (g1["avg_us"] * g1["launches_measured"] + g2["avg_us"] * g2["launches_measured"]) / n_l
+                        kernels["gemm_pooled"] = {"kernel": "c4_head_gemm_kernel, all three hidden-layer launches of a round pooled (as rocprofv3 names them: one instance)",
+                                                  "calls_per_round": n_l / tl_rounds, "avg_us": us, "rocprof_avg_us": rocprof["gemm_pooled"], "flops_per_launch": fl_pooled,
+                                                  "frac_of_mfma_peak": fl_pooled / (us * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
+                                                  "rocprof_frac_of_mfma_peak": fl_pooled / (rocprof["gemm_pooled"] * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS}
+                    if "tower" in kernels and "rocprof_avg_us" in kernels["tower"]:
+                        kernels["tower"]["rocprof_frac_of_mfma_peak"] = kernels["tower"]["flops_per_launch"] / (kernels["tower"]["rocprof_avg_us"] * 1e-6) / 1e12 / MFMA_BF16_PEAK_TFLOPS
+                    if fused and "rocprof_avg_us" in fused:
+                        fused["rocprof_frac_of_hbm_peak"] = fused["algorithmic_bytes_per_launch"] / (fused["rocprof_avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
+                    kernels["rocprof_source"] = f"profiles/{stats_file} (rocprofv3 --kernel-trace --stats of this command; not re-measured in this run)"
+                except Exception:
+                    pass
+                kernels["one_element_kernel_interval_us"] = null_us
+                per_round_us = sum(ms for _l, ms, _n in timeline) * 1e3 / tl_rounds
+                kernels["sum_per_session_round_us"] = per_round_us
+                kernels["share_of_round"] = {label: ms * 1e3 / tl_rounds / per_round_us for label, ms, _n in timeline}
+                kernels["rows_per_launch"] = rows
+                kernels["method"] = (f"{tl_rounds} eager rounds of one session ({rows} rows) right after the timed region, a HIP event on its stream at every launch boundary, queued in batches "
+                                     "behind a blocker so that the GPU runs them back to back; the other session idle (rocprofv3's kernel trace serialises the two queues the same way: "
+                                     "profiles/r06_kernel_stats.csv holds its averages for the same kernels: rocprof_avg_us); an event-to-event interval is the kernel PLUS the dispatch of a dependent launch -- the same "
+                                     "bracket around a chain of one-element kernels gives one_element_kernel_interval_us -- which is why avg_us exceeds rocprof_avg_us by 2.5-3.5 us")
+            issue = None   # the step kernel's issue-slot occupancy, from the committed counter summary (own rocprofv3 --pmc passes, tools/profile/run_r06.sh)
+            try:
+                pmc_step = next(f for f in ("r06_step_kernel_pmc.json", "r05_step_kernel_pmc.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
+                pw = json.load(open(os.path.join(ROOT, "profiles", pmc_step)))["games_65536"]["per_wave"]
+                waves_per_simd = 4   # 127-128 VGPRs: four wavefronts share a SIMD
+                issue = {"issue_slots_taken": pw["SQ_ACTIVE_INST_ANY_per_wave"] * waves_per_simd / pw["SQ_WAVE_CYCLES_per_wave"],
+                         "valu_share_of_issue": pw["SQ_ACTIVE_INST_VALU_per_wave"] / pw["SQ_ACTIVE_INST_ANY_per_wave"],
+                         "valu_pipe_busy": pw["SQ_ACTIVE_INST_VALU_per_wave"] * waves_per_simd / pw["SQ_WAVE_CYCLES_per_wave"],
+                         "insts_per_wavefront": {k: pw[f"SQ_INSTS_{k}_per_wave"] for k in ("VALU", "SALU", "LDS", "VMEM_RD", "VMEM_WR")},
+                         "waves_per_simd": waves_per_simd, "at_games_per_launch": 65536,
+                         "formula": "issue_slots_taken = SQ_ACTIVE_INST_ANY x wavefronts per SIMD / SQ_WAVE_CYCLES (both in quad-cycles per wavefront): the share of a SIMD's cycles in which one of its "
+                                    "wavefronts issues (an upper bound on the issue stage's load: different instruction types of different wavefronts can issue together); valu_pipe_busy = the same "
+                                    "with SQ_ACTIVE_INST_VALU: the vector ALU's own occupancy",
+                         "source": f"profiles/{pmc_step} (rocprofv3 --pmc, own passes; stand-alone c4_step_kernel = the step_body the fused launch runs); not re-measured in this run"}
+            except Exception:
+                pass
+            roofline = {"bound": "hbm",
+                        "kernel": ("c4_out_step_kernel: the launch of the timed region -- the heads' output layers, then expand + backup + move + select + encode of the same games"
+                                   if fused else "c4_step_kernel (expand+backup+move+select+encode, fused)"),
+                        "measured_on": ("the event-bracketed rounds right after the timed region (see kernels.method); `achieved` = SURVEY 8(d)'s tree bytes (92 S + 28 K + 332 E + encode, "
+                                        "device-counted) per launch / this launch's average duration -- the output layers' own operands (head_out_operand_bytes_per_launch) are not counted"
+                                        if fused else "the instrumented stand-alone launches after the timed region"),
+                        "achieved": fused["achieved_gbps"] if fused else achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": (fused["achieved_gbps"] if fused else achieved) / HBM_PEAK_GBPS,
+                        "avg_launch_us": fused["avg_us"] if fused else avg_kernel_s * 1e6,
+                        "launches_measured": fused["launches_measured"] if fused else n_inst, "games_per_launch": sess.rows,
+                        "algorithmic_bytes_per_launch": fused["algorithmic_bytes_per_launch"] if fused else ab["total"] / n_inst,
+                        "head_out_operand_bytes_per_launch": (rows * 2 * F * 2 + 9 * F * 2 + rows * 36) if fused else None,
+                        "traffic": traffic_fused if fused else traffic,
+                        "traffic_source": "profiles/step_kernel_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, each in its own run, corrected per MI355X_MICROARCH.md); not re-measured in this run",
+                        "traffic_collected_on_this_step_kernel": traffic_current,
+                        # what binds it: not bytes.  At every launch size the SIMDs' issue slots are what is full (VALU above all), see DESIGN.md 4.2
+                        "binding_roof": "valu_issue", "issue_slot_occupancy": issue,
+                        "step_alone": {
+                            "kernel": "c4_step_kernel (the same step_body as a launch of its own: per-launch device-clock timing needs it; what the callback mode and eager sessions run)",
+                            "achieved": achieved, "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                            # the memory system's ceiling for THIS access pattern (random whole 128-byte lines from an HBM-resident table,
+                            # tools/gather_lab.hip): 6.7 TB/s, i.e. 84 % of the 8 TB/s the fraction above is quoted against
+                            "frac_of_practical_ceiling": achieved / 6700.0,
+                            "device_clock_frac_of_practical_ceiling": achieved_dev / 6700.0,
+                            "avg_launch_us": avg_kernel_s * 1e6,
+                            "device_clock": {"avg_kernel_us": dev_s * 1e6, "achieved": achieved_dev, "frac": achieved_dev / HBM_PEAK_GBPS,
+                                             "note": "in-kernel s_memrealtime stamps; the HIP-event bracket adds the dispatch and completion latency of one launch"},
+                            "launches_measured": n_inst, "algorithmic_bytes_per_launch": ab["total"] / n_inst},
+                        "practical_ceilings": {"random_128B_lines_from_HBM_GBps": 6700, "dependent_line_chain_ns_per_level_idle": 550,
+                                               "source": "profiles/r02_gather_lab.jsonl (tools/gather_lab.hip on MI355X): what the memory system gives the tree walk's access pattern; at this launch size the kernel is bound by one wavefront's dependent chain, not by bytes (DESIGN.md 4.2)"},
+                        "bytes_per_sim": {k: v / max(1, di["sims"]) for k, v in ab.items()},
+                        "S_per_sim": di["select_levels"] / max(1, di["sims"]), "K_per_sim": di["backup_nodes"] / max(1, di["sims"]),
+                        "E_per_sim": di["expansions"] / max(1, di["sims"]),
+                        "kernels": kernels or None}
         shape = (G, n_iter, cfg.n_residual_blocks, cfg.conv_filter_size)
         named = {(4096, 100, 4, 32): "BASELINE config 2 per GPU", (4096, 800, 8, 64): "BASELINE config 4",
                  (8192, 200, 8, 64): "BASELINE config 5's per-GPU share (temperature schedule on, Dirichlet noise " + (f"alpha,eps = {args.dirichlet}" if args.dirichlet else "off") + ")"
@@ -1026,40 +1070,7 @@ def main():
                             "note": "EXTENSION switched on by --eval-cache: repeated positions skip the evaluator; not the headline configuration"}
                            if args.eval_cache else None),
             "sims_per_game": sims / max(1.0, games),
-            "roofline": {"bound": "hbm",
-                         "kernel": ("c4_out_step_kernel: the launch of the timed region -- the heads' output layers, then expand + backup + move + select + encode of the same games"
-                                    if fused else "c4_step_kernel (expand+backup+move+select+encode, fused)"),
-                         "measured_on": ("the event-bracketed rounds right after the timed region (see kernels.method); `achieved` = SURVEY 8(d)'s tree bytes (92 S + 28 K + 332 E + encode, "
-                                         "device-counted) per launch / this launch's average duration -- the output layers' own operands (head_out_operand_bytes_per_launch) are not counted"
-                                         if fused else "the instrumented stand-alone launches after the timed region"),
-                         "achieved": fused["achieved_gbps"] if fused else achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": (fused["achieved_gbps"] if fused else achieved) / HBM_PEAK_GBPS,
-                         "avg_launch_us": fused["avg_us"] if fused else avg_kernel_s * 1e6,
-                         "launches_measured": fused["launches_measured"] if fused else n_inst, "games_per_launch": sess.rows,
-                         "algorithmic_bytes_per_launch": fused["algorithmic_bytes_per_launch"] if fused else ab["total"] / n_inst,
-                         "head_out_operand_bytes_per_launch": (rows * 2 * F * 2 + 9 * F * 2 + rows * 36) if fused else None,
-                         "traffic": traffic_fused if fused else traffic,
-                         "traffic_source": "profiles/step_kernel_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, each in its own run, corrected per MI355X_MICROARCH.md); not re-measured in this run",
-                         "traffic_collected_on_this_step_kernel": traffic_current,
-                         # what binds it: not bytes.  At every launch size the SIMDs' issue slots are what is full (VALU above all), see DESIGN.md 4.2
-                         "binding_roof": "valu_issue", "issue_slot_occupancy": issue,
-                         "step_alone": {
-                             "kernel": "c4_step_kernel (the same step_body as a launch of its own: per-launch device-clock timing needs it; what the callback mode and eager sessions run)",
-                             "achieved": achieved, "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                             # the memory system's ceiling for THIS access pattern (random whole 128-byte lines from an HBM-resident table,
-                             # tools/gather_lab.hip): 6.7 TB/s, i.e. 84 % of the 8 TB/s the fraction above is quoted against
-                             "frac_of_practical_ceiling": achieved / 6700.0,
-                             "device_clock_frac_of_practical_ceiling": achieved_dev / 6700.0,
-                             "avg_launch_us": avg_kernel_s * 1e6,
-                             "device_clock": {"avg_kernel_us": dev_s * 1e6, "achieved": achieved_dev, "frac": achieved_dev / HBM_PEAK_GBPS,
-                                              "note": "in-kernel s_memrealtime stamps; the HIP-event bracket adds the dispatch and completion latency of one launch"},
-                             "launches_measured": n_inst, "algorithmic_bytes_per_launch": ab["total"] / n_inst},
-                         "practical_ceilings": {"random_128B_lines_from_HBM_GBps": 6700, "dependent_line_chain_ns_per_level_idle": 550,
-                                                "source": "profiles/r02_gather_lab.jsonl (tools/gather_lab.hip on MI355X): what the memory system gives the tree walk's access pattern; at this launch size the kernel is bound by one wavefront's dependent chain, not by bytes (DESIGN.md 4.2)"},
-                         "bytes_per_sim": {k: v / max(1, di["sims"]) for k, v in ab.items()},
-                         "S_per_sim": di["select_levels"] / max(1, di["sims"]), "K_per_sim": di["backup_nodes"] / max(1, di["sims"]),
-                         "E_per_sim": di["expansions"] / max(1, di["sims"]),
-                         "kernels": kernels or None},
+            **({"roofline": roofline} if args.full else {}),
             "nn": {"bound": "mfma", "flops_per_leaf": fl, "achieved": fl * G * timed_rounds / elapsed / 1e12,
                    "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                    "frac": fl * G * timed_rounds / elapsed / 1e12 / MFMA_BF16_PEAK_TFLOPS,
@@ -1073,7 +1084,7 @@ def main():
             out["sample_allgather"] = allgather
         if per_rank is not None:
             out["per_rank"] = per_rank
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the checker's leg runs in a child process under a time limit: whatever happens to it, the GPU line is printed
             import subprocess
             for sp in sessions:
@@ -1090,7 +1101,7 @@ def main():
                 out["cpu_baseline"] = json.loads(line[-1])
             except Exception as e:  # the oracle is a checker; its absence must not hide the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "games/s", "cores": 0, "kind": "port", "sample": f"failed: {e!r}"}
-        if world == 1 and not args.no_other_configs and shape == (4096, 100, 4, 32):
+        if args.full and world == 1 and not args.no_other_configs and shape == (4096, 100, 4, 32):
             out["other_configs"] = other_config_legs(args, sessions)
             sessions = []
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

@@ -149,7 +149,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--rounds-per-step", "128",
-           "--preroll", "1600"]
+           "--preroll", "1600", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     out = _check_bench_line(r, 2)
     assert "cpu_baseline" not in out
@@ -169,7 +169,7 @@ def test_bench_at_world_size_eight_on_one_gpu(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "C4_BENCH_SAME_DEVICE", "C4_BENCH_BACKEND"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--rounds-per-step", "128",
-           "--preroll", "1600", "--games-per-gpu", "512"]
+           "--preroll", "1600", "--full", "--games-per-gpu", "512"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     out = _check_bench_line(r, 8)
     assert "cpu_baseline" not in out and out["config"]["parallelism"] == "games sharded id%8"
@@ -183,7 +183,7 @@ def test_bench_over_rccl_at_world_size_one(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "C4_BENCH_BACKEND", "C4_BENCH_SAME_DEVICE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--rounds-per-step", "128",
-           "--preroll", "1600", "--no-cpu-baseline"]
+           "--preroll", "1600", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     _check_bench_line(r, 1)
 
@@ -195,7 +195,7 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     env = dict(os.environ, C4_BENCH_SAME_DEVICE="1", C4_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--rounds-per-step", "128", "--preroll", "1600"]
+           "--rounds-per-step", "128", "--preroll", "1600", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     out = _check_bench_line(r, 2)
     assert "cpu_baseline" not in out                                  # rank 0 at N = 1 only

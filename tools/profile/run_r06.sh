@@ -3,13 +3,13 @@
 # Every step is bounded by its own timeout; the summaries land under gpurun_out/r06p and are copied into profiles/ by hand.
 # Counter passes (--pmc) are their own runs, with --kernel-trace only (never with --stats / other trace domains).
 O=gpurun_out/r06p; mkdir -p $O; export TMPDIR=/tmp
-timeout 600 python bench.py --steps 20 --warmup 1 > $O/bench.json 2> $O/bench.err
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 1 --no-cpu-baseline --no-other-configs > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+timeout 600 python bench.py --steps 20 --warmup 1 --full > $O/bench.json 2> $O/bench.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 1 --full --no-cpu-baseline --no-other-configs > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 cp $(find $O/stats -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv; rm -rf $O/stats
 # HBM traffic of the tree kernel: FETCH_SIZE and WRITE_SIZE, one pass each, of the bench command; summarised for the stand-alone
 # c4_step_kernel (the 300 instrumented launches) and for c4_out_step_kernel (the last 300 launches = the event-bracketed rounds)
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -- python3 bench.py --steps 1 --warmup 1 --rounds-per-step 64 --preroll 640 --instrumented-steps 300 --no-cpu-baseline --no-other-configs > $O/pmc_$c.json 2> $O/pmc_$c.err
+  timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -- python3 bench.py --steps 1 --warmup 1 --rounds-per-step 64 --preroll 640 --instrumented-steps 300 --full --no-cpu-baseline --no-other-configs > $O/pmc_$c.json 2> $O/pmc_$c.err
   python tools/profile/summarize_pmc.py $O/pmc_$c c4_step_kernel 20 > $O/traffic_$c.json
   python tools/profile/summarize_pmc.py $O/pmc_$c c4_out_step_kernel -300 > $O/traffic_fused_$c.json
   rm -rf $O/pmc_$c
