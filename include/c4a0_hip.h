@@ -419,6 +419,20 @@ int c4_dirichlet(const uint64_t* game_id_dev, const uint32_t* n_moves_dev, const
 int c4_sample_move(const uint64_t* game_id_dev, const uint32_t* n_moves_dev, const float* policy_dev,
                    const float* temperature_dev, uint64_t n, int32_t* out_col_dev, uint32_t* out_u32_dev, void* stream);
 
+/* ---- bf16 evaluator (c4_conv_tower_bf16, c4_linear_bf16, c4_head_out_bf16): where the chain rounds.  Every product of two bf16
+ * operands is accumulated in f32 (MFMA, in an order of the kernel's own: only the f32 accumulation order is unspecified), and a
+ * value is rounded to bf16 -- round to nearest, ties to even (v_cvt_pk_bf16_f32) -- at these points and nowhere else:
+ *   conv0        y = bf16(s), s = the f32 sum of the products started at the bias (so in every tower layer; no activation)
+ *   block conv 1 t = bf16(s)  (no activation: the ReLU comes after the second conv)
+ *   block conv 2 y = bf16(x + relu(s)), s with the BN-folded weights and bias, x the block's bf16 input widened exactly to f32, the
+ *                add one f32 operation
+ *   linear       y = bf16(act(acc + bias[n])), act = relu or none, the bias added in f32 after the k-loop
+ *   head out     v = acc + bias in f32 (no bf16 rounding); log-softmax and tanh in f32 (device expf / logf / tanhf)
+ * Biases: the tower's (conv0, both convs of each block, BN folded) and the output layers' are f32; the hidden layers' biases are
+ * rounded to bf16 by c4a0_amd/nn.py::InferenceNet (the weights and biases of the heads are bf16 tensors there) and widened back to f32
+ * for c4_linear_bf16's epilogue.  Tower weights and hidden / output weights are bf16.  tests/bf16_ref.py restates the chain in
+ * float64 and tests/test_gpu_bf16_exact.py holds the kernels to it bit for bit on data whose every partial sum is exact in f32. */
+
 /* ---- evaluator building block: the residual conv tower of ConnectFourNet (src/c4a0/nn.py:64-70,
  * 184-195; eval-mode BatchNorm folded into the second conv of each block) as one MFMA kernel.
  *   planes_dev bf16 [n_boards][2][6][7] (what c4_session_step writes with planes_dtype = 1)

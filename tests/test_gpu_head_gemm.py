@@ -21,21 +21,42 @@ def _linear(L, x, w, b32, relu=1, config=0, out=None):
     return y
 
 
-@pytest.fixture(scope="module")
-def ops():
+def _operands(k, n):
     from c4a0_amd import _lib
     torch.manual_seed(7)
     dev = torch.device("cuda:0")
-    k, n = 1344, 2688
     x = torch.randn(2048, k, device=dev).to(torch.bfloat16)
     w = (torch.randn(n, k, device=dev) / k ** 0.5).to(torch.bfloat16)
     b = torch.randn(n, device=dev)
     return _lib.lib(), x, w, b
 
 
+@pytest.fixture(scope="module")
+def ops():
+    return _operands(1344, 2688)
+
+
+@pytest.fixture(scope="module")
+def ops64():
+    """The 64-channel net's merged first layer: K = 2 688 (42 k-tiles of 64), N = 5 376."""
+    return _operands(2688, 5376)
+
+
 @pytest.mark.parametrize("config", [0] + CONFIGS)
 @pytest.mark.parametrize("m", [1, 77, 300, 2048])
 def test_matches_fp32_reference(ops, config, m):
+    _check_fp32_reference(ops, config, m)
+
+
+@pytest.mark.parametrize("config", [0] + CONFIGS)
+@pytest.mark.parametrize("m", [1, 77, 300, 2048])
+def test_matches_fp32_reference_at_k2688(ops64, config, m):
+    """The same check on the 64-channel net's merged first layer (K = 2 688: a different ring residue of the k-tiles, and the
+    automatic choice's k >= 2 048 table)."""
+    _check_fp32_reference(ops64, config, m)
+
+
+def _check_fp32_reference(ops, config, m):
     L, x, w, b = ops
     for relu in (1, 0):
         y = _linear(L, x[:m], w, b, relu=relu, config=config)
