@@ -21,6 +21,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 import torch
 
+from ._lib import check, lib
 from .results import GameMetadata, PlayGamesResult, results_from_records
 from .session import DeviceEvaluator, DeviceSession
 
@@ -85,10 +86,6 @@ class _CallbackEvaluator:
     float32 [B, 2, 6, 7], unique positions, B <= max_nn_batch_size, one model per call."""
 
     def __init__(self, session: DeviceSession, cb: Callable, max_nn_batch_size: int, p0: np.ndarray, p1: np.ndarray):
-        import ctypes as C
-
-        from ._lib import check
-        self._C, self._check = C, check
         self.s, self.cb, self.cap = session, cb, max(1, int(max_nn_batch_size))
         dev, g = session.device, session.n_slots
         self.models_used = np.unique(np.concatenate([p0, p1]))
@@ -102,15 +99,14 @@ class _CallbackEvaluator:
         self.nn_positions = 0
 
     def __call__(self, _planes: torch.Tensor, fused_step: bool = False):
-        s, C = self.s, self._C
+        s = self.s
         g = s.n_slots
         # A FRESH pinned array per step (PyTorch's caching host allocator: no system call after warm-up), as the
         # reference hands its callback a new array it owns (pybridge.rs:220 into_pyarray): a callback that keeps x
         # keeps this block alive, nothing it was given is ever overwritten.
         h_planes = torch.empty((g, 2, 6, 7), dtype=torch.float32, pin_memory=True)
-        self._check(s.L.c4_session_unique_leaves(s._h, C.c_void_p(self.inverse.data_ptr()), C.c_void_p(h_planes.data_ptr()),
-                                                 C.c_void_p(self.h_models.data_ptr()) if self.multi else None,
-                                                 C.c_void_p(self.h_count.data_ptr())))
+        check(s.L.c4_session_unique_leaves(s._h, self.inverse.data_ptr(), h_planes.data_ptr(),
+                                           self.h_models.data_ptr() if self.multi else None, self.h_count.data_ptr()))
         s._bound_stream.synchronize()              # the batch and its size have landed in host memory
         n_u = int(self.h_count[0])
         if n_u == 0:                               # every resident game has finished
@@ -140,9 +136,9 @@ class _CallbackEvaluator:
         # h_out is read by the kernel on the session's stream; the next write to it happens after the next step's
         # synchronisation above, which that kernel precedes
         if fused_step:   # the step kernel itself takes every game's answers from its row (c4_session_step_gather): one launch less
-            self._check(s.L.c4_session_step_gather(s._h, C.c_void_p(self.inverse.data_ptr()), C.c_void_p(self.h_out.data_ptr()), n_u))
+            check(s.L.c4_session_step_gather(s._h, self.inverse.data_ptr(), self.h_out.data_ptr(), n_u))
             return None
-        self._check(s.L.c4_session_scatter_outputs(s._h, C.c_void_p(self.inverse.data_ptr()), C.c_void_p(self.h_out.data_ptr()), n_u))
+        check(s.L.c4_session_scatter_outputs(s._h, self.inverse.data_ptr(), self.h_out.data_ptr(), n_u))
         return s.logprobs, s.q
 
     gather_step = True   # round(): scatter + step as one launch (False: A/B)
@@ -454,8 +450,6 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
 def trim_cached_memory() -> None:
     """Give the tree arena that the library keeps for the next session (c4_trim_cached_memory, include/c4a0_hip.h)
     back to the device: for callers that want every byte of HBM between two self-play phases."""
-    from ._lib import check, lib
-
     check(lib().c4_trim_cached_memory())
 
 

@@ -14,14 +14,18 @@ kernel reads and writes.
 """
 from __future__ import annotations
 
+import ctypes
 import threading
 import warnings
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from ._lib import check, lib
 
 N_COLS, N_ROWS = 7, 6
 
@@ -154,19 +158,195 @@ def pack_f32_weights(conv_w, conv_b, pol_w, pol_b, val_w, val_b, channels: int) 
             "pol_w": pw, "pol_b": pb, "val_w": vw, "val_b": vb}
 
 
+def fold_network(model: ConnectFourNet):
+    """The network as BN-folded f32 host weights (eval-mode statistics), reference layout (the heads' first layers read
+    "c h w", nn.py:111): (conv_w, conv_b, pol_w, pol_b, val_w, val_b), each a list -- the first conv and every block's two;
+    one entry per Linear of a head, the output layer last."""
+    conv0 = model.conv[0]
+    conv_w, conv_b = [conv0.weight.detach().float()], [conv0.bias.detach().float()]
+    for blk in list(model.conv)[1:]:
+        c1, c2, bn = blk.block[0], blk.block[1], blk.block[2]
+        w, b = _fold_bn(c2.weight, c2.bias, bn)
+        conv_w += [c1.weight.detach().float(), w]
+        conv_b += [c1.bias.detach().float(), b]
+
+    def head(seq):
+        mods = list(seq)
+        folded = [_fold_bn(m[0].weight, m[0].bias, m[1]) for m in mods[:-2]]
+        folded.append((mods[-2].weight.detach().float(), mods[-2].bias.detach().float()))
+        return [w for w, _ in folded], [b for _, b in folded]
+
+    return (conv_w, conv_b, *head(model.fc_policy), *head(model.fc_value))
+
+
+def _stream(device: torch.device) -> int:
+    """The current stream of `device`, as the handle the library's entry points take."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+class _TorchChain:
+    """A kernel chain: InferenceNet constructs exactly one, from fold_network()'s weights, and calls it for everything that
+    touches a kernel -- tower(), linear_relu() (one hidden layer), head_out() (both output layers) and, on the HIP chains,
+    np_planes() (the head of forward_numpy's graph: it leaves the planes to evaluate).  It owns its operands on the device:
+    conv_w ... val_b, pol_b32 / val_b32, _bias32, and tw0 / tw / tbias / cp / hp where it has them.
+
+    This one is PyTorch's kernels in `dtype` (F.conv2d, the library GEMM, F.linear + log_softmax / tanh; reference layout; a
+    position's low bits depend on the batch) and the base of the two HIP chains, which replace all three operations."""
+    np_planes = None        # no graph: forward_numpy is a plain forward and a copy back
+    np_converts = False     # np_planes() is c4_planes_from_f32: from the f32 batch the pinned slot (c4_f32_batch) points at, on the
+                            # device or in pinned host memory, to the state's bf16 planes
+
+    def __init__(self, folded, device: torch.device, dtype: torch.dtype):
+        conv_w, conv_b, pol_w, pol_b, val_w, val_b = folded
+        self.device, self.dtype = device, dtype
+        mv = lambda ts: [t.to(device, dtype).contiguous() for t in ts]
+        self.conv_w = [w.to(device, dtype).contiguous(memory_format=torch.channels_last) for w in conv_w]
+        self.conv_b, self.pol_w, self.pol_b, self.val_w, self.val_b = mv(conv_b), mv(pol_w), mv(pol_b), mv(val_w), mv(val_b)
+        self.pol_b32 = pol_b[-1].to(device, torch.float32).contiguous()
+        self.val_b32 = val_b[-1].to(device, torch.float32).contiguous()
+        self.fused_epilogue = device.type == "cuda" and hasattr(torch, "_addmm_activation")   # bias and ReLU in the GEMM's epilogue
+        self._bias32 = {}   # f32 copies of the hidden layers' biases for c4_linear_bf16's epilogue, by bias tensor
+
+    def hidden_bias_added(self, b: torch.Tensor):
+        """linear_relu() will be handed `b` (the merged first layer's bias) like the biases this chain made itself."""
+
+    def tower(self, planes, config=0):
+        x = planes.to(self.dtype)
+        x = F.conv2d(x, self.conv_w[0], self.conv_b[0], padding=1)
+        for i in range(1, len(self.conv_w), 2):
+            y = F.conv2d(x, self.conv_w[i], self.conv_b[i], padding=1)
+            y = F.conv2d(y, self.conv_w[i + 1], self.conv_b[i + 1], padding=1)
+            x = x + F.relu(y)
+        return x.reshape(x.shape[0], -1)
+
+    def linear_relu(self, x, w, b, out=None, config=0):
+        if self.fused_epilogue:
+            return torch._addmm_activation(b, x, w.t(), use_gelu=False)
+        return F.relu(F.linear(x, w, b))
+
+    def head_out(self, p, v, out_logprobs=None, out_q=None):
+        p = F.linear(p, self.pol_w[-1], self.pol_b[-1]).float()
+        v = F.linear(v, self.val_w[-1], self.val_b[-1]).float()
+        return torch.log_softmax(p, dim=1, out=out_logprobs), torch.tanh(v, out=out_q)
+
+
+class _Bf16Chain(_TorchChain):
+    """The product: c4_conv_tower_bf16, c4_linear_bf16, c4_head_out_bf16 (32 or 64 channels).  The base's bf16 operands with the
+    heads' first layers permuted to the tower's cell-major features; hip_gemm=False (gemm="hipblaslt", the A/B switch) keeps
+    the base's library GEMM for the hidden layers."""
+    np_converts = True
+
+    def __init__(self, folded, device: torch.device, hip_gemm: bool):
+        conv_w, conv_b, pol_w, pol_b, val_w, val_b = folded
+        c = self.channels = conv_w[0].shape[0]
+        # the tower emits [cell][channel]; the reference flattens "c h w" (nn.py:111): permute
+        # the input dimension of each head's first Linear once instead of the activations
+        perm = lambda wt: wt.reshape(wt.shape[0], c, 42).permute(0, 2, 1).reshape(wt.shape[0], 42 * c)
+        super().__init__((conv_w, conv_b, [perm(pol_w[0])] + pol_w[1:], pol_b, [perm(val_w[0])] + val_w[1:], val_b), device, torch.bfloat16)
+        self.L: ctypes.CDLL = lib()
+        self.n_blocks, self.hip_gemm = len(conv_w) // 2, hip_gemm
+        w0, w, bias = pack_tower_weights(conv_w, conv_b, c)
+        self.tw0, self.tw = w0.to(device, torch.bfloat16).contiguous(), w.to(device, torch.bfloat16).contiguous()
+        self.tbias = bias.to(device, torch.float32).contiguous()
+        for b in self.pol_b[:-1] + self.val_b[:-1]:
+            self.hidden_bias_added(b)
+
+    def hidden_bias_added(self, b):
+        if self.hip_gemm:
+            self._bias32[b.data_ptr()] = b.float().contiguous()
+
+    def np_planes(self, st: dict, bucket: int):
+        check(self.L.c4_planes_from_f32(st["slot"].data_ptr(), None, 0, st["planes"].data_ptr(), bucket, _stream(self.device)))
+        return st["planes"][:bucket]
+
+    def tower(self, planes, config=0):
+        x = planes.to(torch.bfloat16).contiguous()
+        g = x.shape[0]
+        out = torch.empty((g, 42 * self.channels), dtype=torch.bfloat16, device=self.device)
+        check(self.L.c4_conv_tower_bf16(x.data_ptr(), self.tw0.data_ptr(), self.tw.data_ptr(), self.tbias.data_ptr(),
+                                        g, self.channels, self.n_blocks, out.data_ptr(), config, _stream(self.device)))
+        return out
+
+    def linear_relu(self, x, w, b, out=None, config=0):
+        if not self.hip_gemm:
+            return super().linear_relu(x, w, b)
+        assert x.stride(1) == 1 and w.is_contiguous()
+        m, (n, k) = x.shape[0], w.shape
+        y = out if out is not None else torch.empty((m, n), dtype=torch.bfloat16, device=self.device)
+        check(self.L.c4_linear_bf16(x.data_ptr(), w.data_ptr(), self._bias32[b.data_ptr()].data_ptr(), y.data_ptr(),
+                                    m, n, k, x.stride(0), y.stride(0), 1, config, _stream(self.device)))
+        return y
+
+    def head_out(self, p, v, out_logprobs=None, out_q=None):
+        # both output layers + log-softmax + tanh in one HIP launch, written in place
+        g = p.shape[0]
+        lp = out_logprobs if out_logprobs is not None else torch.empty((g, 7), dtype=torch.float32, device=self.device)
+        q = out_q if out_q is not None else torch.empty((g, 2), dtype=torch.float32, device=self.device)
+        assert p.stride(1) == 1 and v.stride(1) == 1
+        check(self.L.c4_head_out_bf16(p.data_ptr(), v.data_ptr(), self.pol_w[-1].data_ptr(), self.val_w[-1].data_ptr(),
+                                      self.pol_b32.data_ptr(), self.val_b32.data_ptr(), g, p.shape[1], p.stride(0), v.stride(0),
+                                      lp.data_ptr(), q.data_ptr(), _stream(self.device)))
+        return lp, q
+
+
+class _F32Chain(_TorchChain):
+    """c4_conv_tower_f32, c4_linear_f32, c4_head_out_f32 (1 to 64 channels): every product an exact-f32 MFMA fmaf chain in the
+    documented order (include/c4a0_hip.h), so a row's outputs depend on that row alone and equal tests/f32_net_ref.c bit for
+    bit.  Operands in pack_f32_weights' padded layouts (cp channels, hp hidden features); no unpacked conv weights are kept."""
+
+    def __init__(self, folded, device: torch.device):
+        pk = pack_f32_weights(*folded, folded[0][0].shape[0])
+        super().__init__(([], [], pk["pol_w"], pk["pol_b"], pk["val_w"], pk["val_b"]), device, torch.float32)
+        self.L: ctypes.CDLL = lib()
+        self.cp, self.hp, self.n_blocks = pk["cp"], pk["hp"], len(folded[0]) // 2
+        self.tw0, self.tw, self.tbias = (pk[k].to(device, torch.float32).contiguous() for k in ("w0", "w", "bias"))
+
+    def np_planes(self, st: dict, bucket: int):
+        return st["in"][:bucket]   # the f32 positions as they are (rows from the batch's end to `bucket`: earlier batches, unread)
+
+    def tower(self, planes, config=0):
+        x = planes.float().contiguous()
+        g = x.shape[0]
+        out = torch.empty((g, 42 * self.cp), dtype=torch.float32, device=self.device)
+        work = torch.empty_like(out) if self.n_blocks else None
+        check(self.L.c4_conv_tower_f32(x.data_ptr(), self.tw0.data_ptr(), self.tw.data_ptr(), self.tbias.data_ptr(), g, self.cp, self.n_blocks,
+                                       out.data_ptr(), work.data_ptr() if work is not None else None, _stream(self.device)))
+        return out
+
+    def linear_relu(self, x, w, b, out=None, config=0):
+        assert x.stride(1) == 1 and w.is_contiguous()
+        m, (n, k) = x.shape[0], w.shape
+        y = out if out is not None else torch.empty((m, n), dtype=torch.float32, device=self.device)
+        check(self.L.c4_linear_f32(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), m, n, k, x.stride(0), y.stride(0), 1, _stream(self.device)))
+        return y
+
+    def head_out(self, p, v, out_logprobs=None, out_q=None, out_preact=None):
+        """Both output layers, log-softmax and tanh written in place (out_preact [G, 9]: the pre-activations too)."""
+        g = p.shape[0]
+        lp = out_logprobs if out_logprobs is not None else torch.empty((g, 7), dtype=torch.float32, device=self.device)
+        q = out_q if out_q is not None else torch.empty((g, 2), dtype=torch.float32, device=self.device)
+        assert p.stride(1) == 1 and v.stride(1) == 1
+        check(self.L.c4_head_out_f32(p.data_ptr(), v.data_ptr(), self.pol_w[-1].data_ptr(), self.val_w[-1].data_ptr(),
+                                     self.pol_b32.data_ptr(), self.val_b32.data_ptr(), g, self.pol_w[-1].shape[1], self.val_w[-1].shape[1], p.stride(0),
+                                     v.stride(0), lp.data_ptr(), q.data_ptr(), out_preact.data_ptr() if out_preact is not None else None, _stream(self.device)))
+        return lp, q
+
+
 class EvaluatorFallbackWarning(UserWarning):
-    """An InferenceNet that leaves the hand-written HIP kernels (channels not 32 / 64, or not bf16, or not on a HIP device)."""
+    """An InferenceNet on a HIP device that runs neither hand-written chain: not bf16 with 32 or 64 channels (the bf16 chain),
+    and not f32 with hip_tower=True (the f32 chain, 1 to 64 channels), so PyTorch's kernels evaluate it."""
 
 
 class InferenceNet:
     """Device-resident evaluator: planes[G,2,6,7] -> (policy_logprobs[G,7] f32, q[G,2] f32).
 
-    `hip_tower=True` (default on a HIP device in bf16 with 32 or 64 channels) runs the conv tower
-    as the hand-written MFMA kernel `c4_conv_tower_bf16`; with dtype=torch.float32 it selects the f32 chain instead
-    (c4_conv_tower_f32 + c4_linear_f32 + c4_head_out_f32: exact-f32 MFMA, any width 1..64, batch-invariant); otherwise PyTorch-ROCm convs + the library GEMM -- a path
-    whose low bits depend on the batch (`batch_invariant` False), slower, and never the one the parity suite certifies.
-    Leaving the hand-written kernels is therefore LOUD: `strict=True` refuses (ValueError), the default warns once per
-    construction (EvaluatorFallbackWarning) and `path` says which one runs ("hip" | "torch"; the bench line carries it)."""
+    BatchNorm is folded into the preceding conv / linear (fold_network) and ONE kernel chain is constructed, whose operands are
+    readable here under its names (_CHAIN_OPERANDS).  `hip_tower=True` (default on a HIP device in bf16 with 32 or 64 channels) is
+    _Bf16Chain; with dtype=torch.float32 it is _F32Chain instead (exact-f32 MFMA, any width 1..64, batch-invariant like the first);
+    otherwise _TorchChain: PyTorch-ROCm convs + the library GEMM -- a path whose low bits depend on the batch (`batch_invariant`
+    False), slower, and never the one the parity suite certifies.  Leaving the hand-written kernels is therefore LOUD:
+    `strict=True` refuses (ValueError), the default warns once per construction (EvaluatorFallbackWarning) and `path` says
+    which one runs ("hip" | "torch"; the bench line carries it)."""
 
     latency_mode = False  # True while ONE session plays alone on the device (api._play sets it): the narrow layers of a
                           # > 1 024-row batch then use the 128 x 96 tile (12.7 vs 16.8 us alone at 1 700 rows; beside a
@@ -176,6 +356,8 @@ class InferenceNet:
     stage_hook = None  # optional callable(stage): 0 = before the tower is launched, 2 = after it, 1 = after the first hidden layer's
                        # GEMM is launched, 3 + i = after the policy head's i-th further layer (session.capture_pair records /
                        # waits cross-stream events there)
+    _CHAIN_OPERANDS = frozenset(("tw0", "tw", "tbias", "conv_w", "conv_b", "pol_w", "pol_b", "val_w", "val_b", "pol_b32", "val_b32",
+                                 "_bias32", "cp", "hp"))
 
     def __init__(self, model: ConnectFourNet, device: torch.device, dtype: torch.dtype = torch.bfloat16,
                  hip_tower: Optional[bool] = None, gemm: Optional[str] = None, gemm_config=None, tower_config: int = 0,
@@ -184,18 +366,18 @@ class InferenceNet:
         A/B switch: its low bits depend on the batch shape).  gemm_config: c4_linear_bf16's tile configuration, one number or
         "wide,narrow" (the merged 2F-wide first layer, the F-wide layers); tower_config: c4_conv_tower_bf16's workgroup
         shape; 0 / None = automatic.  Measurement switches are constructor arguments: nothing is read from the environment."""
-        self.device = torch.device(device)
-        self.dtype = dtype
+        self.device, self.dtype = torch.device(device), dtype
         model = model.eval()
         self.channels = model.config.conv_filter_size
+        self.n_blocks = len(model.conv) - 1
         # f32 networks on the hand-written path only when asked for (hip_tower=True): the f32 chain has no bf16 switches
-        self.f32 = dtype == torch.float32 and bool(hip_tower)
-        if self.f32:
+        f32 = dtype == torch.float32 and bool(hip_tower)
+        if f32:
             if self.device.type != "cuda" or not 1 <= self.channels <= 64:
                 raise ValueError("the f32 HIP evaluator needs a HIP device and 1 to 64 channels")
             if gemm not in (None, "hip") or gemm_config is not None or tower_config:
                 raise ValueError("gemm / gemm_config / tower_config are bf16 switches: the f32 HIP evaluator has none")
-        can_tower = self.device.type == "cuda" and ((dtype == torch.bfloat16 and self.channels in (32, 64)) or self.f32)
+        can_tower = self.device.type == "cuda" and ((dtype == torch.bfloat16 and self.channels in (32, 64)) or f32)
         if hip_tower and not can_tower:
             raise ValueError("hip_tower needs a HIP device, bf16 and 32 or 64 channels")
         self.hip_tower = can_tower if hip_tower is None else bool(hip_tower)
@@ -208,60 +390,15 @@ class InferenceNet:
             if strict:
                 raise ValueError(msg + " (strict=True)")
             warnings.warn(msg, EvaluatorFallbackWarning, stacklevel=2)
-        conv0 = model.conv[0]
-        self.conv_w = [conv0.weight.detach().float()]
-        self.conv_b = [conv0.bias.detach().float()]
-        self.n_blocks = len(model.conv) - 1
-        for blk in list(model.conv)[1:]:
-            c1, c2, bn = blk.block[0], blk.block[1], blk.block[2]
-            self.conv_w.append(c1.weight.detach().float())
-            self.conv_b.append(c1.bias.detach().float())
-            w, b = _fold_bn(c2.weight, c2.bias, bn)
-            self.conv_w.append(w)
-            self.conv_b.append(b)
-
-        def head(seq):
-            ws, bs = [], []
-            mods = list(seq)
-            for m in mods[:-2]:
-                w, b = _fold_bn(m[0].weight, m[0].bias, m[1])
-                ws.append(w)
-                bs.append(b)
-            ws.append(mods[-2].weight.detach().float())
-            bs.append(mods[-2].bias.detach().float())
-            return ws, bs
-
-        self.pol_w, self.pol_b = head(model.fc_policy)
-        self.val_w, self.val_b = head(model.fc_value)
-        self._np_lock = threading.Lock()   # forward_numpy keeps ONE pinned slot, stream and graph set per net
-        if self.f32:
-            self._init_f32()
-            return
-        if self.hip_tower:
-            from . import _lib
-
-            self._L = _lib.lib()
-            w0, w, bias = pack_tower_weights(self.conv_w, self.conv_b, self.channels)
-            self.tw0 = w0.to(self.device, torch.bfloat16).contiguous()
-            self.tw = w.to(self.device, torch.bfloat16).contiguous()
-            self.tbias = bias.to(self.device, torch.float32).contiguous()
-            # the tower emits [cell][channel]; the reference flattens "c h w" (nn.py:111): permute
-            # the input dimension of each head's first Linear once instead of the activations
-            c = self.channels
-            perm = lambda wt: wt.reshape(wt.shape[0], c, 42).permute(0, 2, 1).reshape(wt.shape[0], 42 * c)
-            self.pol_w[0] = perm(self.pol_w[0])
-            self.val_w[0] = perm(self.val_w[0])
-        self.pol_b32 = self.pol_b[-1].to(self.device, torch.float32).contiguous()
-        self.val_b32 = self.val_b[-1].to(self.device, torch.float32).contiguous()
-        self.fused_epilogue = self.device.type == "cuda" and hasattr(torch, "_addmm_activation")
-        # Hidden layers of the heads: "hip" = the hand-written MFMA GEMM (c4_linear_bf16), whose result for
-        # a position does not depend on the batch or the row it sits in -- the default wherever the HIP
+        folded = fold_network(model)
+        # Hidden layers of the heads: "hip" = the hand-written MFMA GEMM (c4_linear_bf16; c4_linear_f32 on the f32 chain), whose
+        # result for a position does not depend on the batch or the row it sits in -- the default wherever the HIP
         # tower runs; "hipblaslt" = PyTorch's library GEMM (kept for A/B timing: its low bits depend on
         # the batch shape).
         gemm = gemm or ("hip" if self.hip_tower else "hipblaslt")
         if gemm not in ("hip", "hipblaslt"):
             raise ValueError("gemm must be 'hip' or 'hipblaslt'")
-        if gemm == "hip" and not (self.hip_tower and (42 * self.channels) % 192 == 0):
+        if gemm == "hip" and not (self.hip_tower and (f32 or (42 * self.channels) % 192 == 0)):
             raise ValueError("gemm='hip' needs the HIP tower (bf16, 32 or 64 channels on a HIP device)")
         self.gemm = gemm
         if strict and gemm != "hip":
@@ -273,40 +410,19 @@ class InferenceNet:
         cfg = str(gemm_config if gemm_config is not None else "0").split(",")
         self.gemm_config = (int(cfg[0]), int(cfg[-1]))
         self.tower_config = int(tower_config)   # c4_conv_tower_bf16's config, 0 = automatic
-        mv = lambda ts: [t.to(self.device, dtype).contiguous() for t in ts]
-        self.conv_w = [w.to(self.device, dtype).contiguous(memory_format=torch.channels_last) for w in self.conv_w]
-        self.conv_b = mv(self.conv_b)
-        self.pol_w, self.pol_b, self.val_w, self.val_b = mv(self.pol_w), mv(self.pol_b), mv(self.val_w), mv(self.val_b)
-        self.merged_w1 = self.merged_b1 = None
-        if len(self.pol_w) > 1 and len(self.val_w) > 1:
-            self.merged_w1 = torch.cat([self.pol_w[0], self.val_w[0]], dim=0).contiguous()
-            self.merged_b1 = torch.cat([self.pol_b[0], self.val_b[0]], dim=0).contiguous()
-        self._bias32 = {}   # f32 copies of the hidden layers' biases for the HIP GEMM's epilogue, by bias tensor
-        if self.gemm == "hip":
-            for b in self.pol_b[:-1] + self.val_b[:-1] + ([self.merged_b1] if self.merged_b1 is not None else []):
-                self._bias32[b.data_ptr()] = b.float().contiguous()
+        self._np_lock = threading.Lock()   # forward_numpy keeps ONE pinned slot, stream and graph set per net
+        ch = self.chain = (_F32Chain(folded, self.device) if f32 else _Bf16Chain(folded, self.device, hip_gemm=gemm == "hip") if self.hip_tower
+                           else _TorchChain(folded, self.device, dtype))
+        self.merged_w1 = self.merged_b1 = None   # the first hidden layer of BOTH heads as one 2F-wide layer (forward_hidden)
+        if len(ch.pol_w) > 1 and len(ch.val_w) > 1:
+            self.merged_w1 = torch.cat([ch.pol_w[0], ch.val_w[0]], dim=0).contiguous()
+            self.merged_b1 = torch.cat([ch.pol_b[0], ch.val_b[0]], dim=0).contiguous()
+            ch.hidden_bias_added(self.merged_b1)
 
-    def _init_f32(self):
-        """The f32 chain: every product an exact-f32 MFMA fmaf chain in the documented order (include/c4a0_hip.h), so a row's
-        outputs depend on that row alone (batch_invariant) and equal tests/f32_net_ref.c bit for bit."""
-        from . import _lib
-
-        self._L = _lib.lib()
-        pk = pack_f32_weights(self.conv_w, self.conv_b, self.pol_w, self.pol_b, self.val_w, self.val_b, self.channels)
-        mv = lambda ts: [t.to(self.device, torch.float32).contiguous() for t in ts]
-        self.cp, self.hp = pk["cp"], pk["hp"]
-        self.tw0, self.tw, self.tbias = mv([pk["w0"], pk["w"], pk["bias"]])
-        self.conv_w, self.conv_b = [], []   # the unpacked copies are not kept on the device
-        self.pol_w, self.pol_b, self.val_w, self.val_b = mv(pk["pol_w"]), mv(pk["pol_b"]), mv(pk["val_w"]), mv(pk["val_b"])
-        self.pol_b32, self.val_b32 = self.pol_b[-1], self.val_b[-1]
-        self.merged_w1 = self.merged_b1 = None
-        if len(self.pol_w) > 1 and len(self.val_w) > 1:
-            self.merged_w1 = torch.cat([self.pol_w[0], self.val_w[0]], dim=0).contiguous()
-            self.merged_b1 = torch.cat([self.pol_b[0], self.val_b[0]], dim=0).contiguous()
-        self.hip_tower, self.gemm, self.batch_invariant = True, "hip", True
-        self.gemm_config, self.tower_config = (0, 0), 0
-        self.fused_epilogue = False
-        self._bias32 = {}
+    def __getattr__(self, name):
+        if name in InferenceNet._CHAIN_OPERANDS and "chain" in self.__dict__:
+            return getattr(self.chain, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     @property
     def path(self) -> str:
@@ -318,50 +434,17 @@ class InferenceNet:
         """Conv tower -> flattened features [G, 42*C] (cell-major when hip_tower, else "c h w").  latency: this call's
         answer to `latency_mode` (None = the attribute)."""
         latency = self.latency_mode if latency is None else latency
-        if self.f32:
-            from ._lib import check
-            import ctypes as C
-
-            x = planes if planes.dtype == torch.float32 else planes.float()
-            x = x.contiguous()
-            g = x.shape[0]
-            out = torch.empty((g, 42 * self.cp), dtype=torch.float32, device=self.device)
-            work = torch.empty_like(out) if self.n_blocks else None
-            check(self._L.c4_conv_tower_f32(C.c_void_p(x.data_ptr()), C.c_void_p(self.tw0.data_ptr()), C.c_void_p(self.tw.data_ptr()),
-                                            C.c_void_p(self.tbias.data_ptr()), g, self.cp, self.n_blocks, C.c_void_p(out.data_ptr()),
-                                            C.c_void_p(work.data_ptr() if work is not None else None),
-                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-            return out
-        if self.hip_tower:
-            from ._lib import check
-            import ctypes as C
-
-            x = planes if planes.dtype == torch.bfloat16 else planes.to(torch.bfloat16)
-            x = x.contiguous()
-            g = x.shape[0]
-            out = torch.empty((g, 42 * self.channels), dtype=torch.bfloat16, device=self.device)
-            check(self._L.c4_conv_tower_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(self.tw0.data_ptr()),
-                                             C.c_void_p(self.tw.data_ptr()), C.c_void_p(self.tbias.data_ptr()),
-                                             g, self.channels, self.n_blocks, C.c_void_p(out.data_ptr()),
-                                             # alone on the device (latency_mode): 8 boards per workgroup from 1 025 to 2 048 boards
-                                             # (up to 1 024 boards the automatic choice is already the narrow-launch shape: 2 or 4 boards per workgroup)
-                                             self.tower_config or (2 if (latency and self.channels == 32 and 1024 < g <= 2048) else 0),
-                                             C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-            return out
-        x = planes.to(self.dtype)
-        x = F.conv2d(x, self.conv_w[0], self.conv_b[0], padding=1)
-        for i in range(self.n_blocks):
-            y = F.conv2d(x, self.conv_w[1 + 2 * i], self.conv_b[1 + 2 * i], padding=1)
-            y = F.conv2d(y, self.conv_w[2 + 2 * i], self.conv_b[2 + 2 * i], padding=1)
-            x = x + F.relu(y)
-        return x.reshape(x.shape[0], -1)
+        # c4_conv_tower_bf16's workgroup shape.  Alone on the device (latency_mode): 8 boards per workgroup from 1 025 to 2 048 boards
+        # (up to 1 024 boards the automatic choice is already the narrow-launch shape: 2 or 4 boards per workgroup)
+        config = self.tower_config or (2 if (latency and self.channels == 32 and 1024 < planes.shape[0] <= 2048) else 0)
+        return self.chain.tower(planes, config)
 
     @torch.no_grad()
     def forward_hidden(self, planes: torch.Tensor, latency: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Everything but the heads' output layers: planes -> (policy head's last hidden activations, value head's), bf16
         [G, F] row views (column stride 1; f32 [G, Hp] on the f32 chain, Hp = F padded to a multiple of 32).  The output layers follow in `forward`, or inside the session's fused output +
         step launch (DeviceSession.round, c4_session_step_head_out)."""
-        hook = self.stage_hook
+        hook, ch = self.stage_hook, self.chain
         if hook is not None:
             hook(0)
         x = self.tower(planes, latency)
@@ -374,21 +457,17 @@ class InferenceNet:
             # costs more than the 3.5 us it saves -- the bench halved, 28.0 -> 13.7 k games/s -- and ROCm 7.2's
             # hipStreamEndCapture crashes on a fork from a non-origin stream, tools/capture_nested_fork_repro.py.)
             h = self._linear_relu(x, self.merged_w1, self.merged_b1, latency=latency)
-            if hook is not None:
-                hook(1)
             f = self.merged_w1.shape[0] // 2
-            p, v = h[:, :f], h[:, f:]
-            pol_rest, val_rest = list(zip(self.pol_w[1:-1], self.pol_b[1:-1])), list(zip(self.val_w[1:-1], self.val_b[1:-1]))
-        else:
-            p = v = x
-            pol_rest, val_rest = list(zip(self.pol_w[:-1], self.pol_b[:-1])), list(zip(self.val_w[:-1], self.val_b[:-1]))
-            if hook is not None:   # no merged first layer (a head without hidden layers): the heavy half ends with the tower
-                hook(1)
-        for i, (w, b) in enumerate(pol_rest):
+            p, v, rest = h[:, :f], h[:, f:], slice(1, -1)
+        else:   # no merged first layer (a head without hidden layers): the heavy half ends with the tower
+            p, v, rest = x, x, slice(0, -1)
+        if hook is not None:
+            hook(1)
+        for i, (w, b) in enumerate(zip(ch.pol_w[rest], ch.pol_b[rest])):
             p = self._linear_relu(p, w, b, latency=latency)
             if hook is not None:
                 hook(3 + i)      # after each narrow policy layer (capture_pair's offset_stage)
-        for w, b in val_rest:
+        for w, b in zip(ch.val_w[rest], ch.val_b[rest]):
             v = self._linear_relu(v, w, b, latency=latency)
         return p, v
 
@@ -404,54 +483,18 @@ class InferenceNet:
 
     def head_out_operands(self):
         """(w_policy, w_value, b_policy f32, b_value f32) of the output layers, as the HIP output kernels take them."""
-        return self.pol_w[-1], self.val_w[-1], self.pol_b32, self.val_b32
+        ch = self.chain
+        return ch.pol_w[-1], ch.val_w[-1], ch.pol_b32, ch.val_b32
 
     @torch.no_grad()
     def forward(self, planes: torch.Tensor, out_logprobs: Optional[torch.Tensor] = None,
                 out_q: Optional[torch.Tensor] = None, latency: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         p, v = self.forward_hidden(planes, latency)
-        if self.f32:
-            return self._head_out_f32(p, v, out_logprobs, out_q)
-        if self.hip_tower:
-            # both output layers + log-softmax + tanh in one HIP launch, written in place
-            from ._lib import check
-            import ctypes as C
-
-            g = p.shape[0]
-            lp = out_logprobs if out_logprobs is not None else torch.empty((g, 7), dtype=torch.float32, device=self.device)
-            q = out_q if out_q is not None else torch.empty((g, 2), dtype=torch.float32, device=self.device)
-            assert p.stride(1) == 1 and v.stride(1) == 1
-            check(self._L.c4_head_out_bf16(C.c_void_p(p.data_ptr()), C.c_void_p(v.data_ptr()),
-                                           C.c_void_p(self.pol_w[-1].data_ptr()), C.c_void_p(self.val_w[-1].data_ptr()),
-                                           C.c_void_p(self.pol_b32.data_ptr()), C.c_void_p(self.val_b32.data_ptr()),
-                                           g, p.shape[1], p.stride(0), v.stride(0), C.c_void_p(lp.data_ptr()), C.c_void_p(q.data_ptr()),
-                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-            return lp, q
-        p = F.linear(p, self.pol_w[-1], self.pol_b[-1]).float()
-        v = F.linear(v, self.val_w[-1], self.val_b[-1]).float()
-        if out_logprobs is None:
-            lp = torch.log_softmax(p, dim=1)
-        else:
-            lp = torch.log_softmax(p, dim=1, out=out_logprobs)
-        q = torch.tanh(v) if out_q is None else torch.tanh(v, out=out_q)
-        return lp, q
+        return self.chain.head_out(p, v, out_logprobs, out_q)
 
     def _head_out_f32(self, p, v, out_logprobs=None, out_q=None, out_preact=None):
-        """c4_head_out_f32: both output layers, log-softmax and tanh written in place (out_preact [G, 9]: the pre-activations too)."""
-        from ._lib import check
-        import ctypes as C
-
-        g = p.shape[0]
-        lp = out_logprobs if out_logprobs is not None else torch.empty((g, 7), dtype=torch.float32, device=self.device)
-        q = out_q if out_q is not None else torch.empty((g, 2), dtype=torch.float32, device=self.device)
-        assert p.stride(1) == 1 and v.stride(1) == 1
-        check(self._L.c4_head_out_f32(C.c_void_p(p.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(self.pol_w[-1].data_ptr()),
-                                      C.c_void_p(self.val_w[-1].data_ptr()), C.c_void_p(self.pol_b32.data_ptr()), C.c_void_p(self.val_b32.data_ptr()),
-                                      g, self.pol_w[-1].shape[1], self.val_w[-1].shape[1], p.stride(0), v.stride(0),
-                                      C.c_void_p(lp.data_ptr()), C.c_void_p(q.data_ptr()),
-                                      C.c_void_p(out_preact.data_ptr() if out_preact is not None else None),
-                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        return lp, q
+        """The f32 chain's c4_head_out_f32 with its extra output (out_preact [G, 9]: the pre-activations too)."""
+        return self.chain.head_out(p, v, out_logprobs, out_q, out_preact)
 
     # ---------------------------------------------------------------- the reference's numpy entry point
     _NP_BUCKET = 128
@@ -463,23 +506,18 @@ class InferenceNet:
         what the reference's callers hand to `play_games` as `lambda model_id, x: model.forward_numpy(x)`
         (training.py:179-189), so a caller that swaps its model for this class keeps its callback.
 
-        The reference's version is a host round trip around ~35 eager launches.  Here ONE HIP-graph replay and one stream
+        The reference's version is a host round trip around ~35 eager launches.  Here, on the HIP chains, ONE HIP-graph replay and one stream
         synchronisation: the graph (captured once per batch size rounded up to a multiple of 128 rows: the kernels compute a
         row from that row alone, so padding rows change nothing) is c4_planes_from_f32 + tower + GEMMs + output kernel, and
         the output kernel writes into pinned host memory itself.  The f32 network (hip_tower=True) reads f32 positions as they
-        are: the batch is copied into the graph's device input (no conversion kernel), then the same one replay.  A batch that already lives in pinned host memory -- what
+        are: the batch is copied into the graph's device input (no conversion kernel), then the same one replay.  On the bf16 chain a batch that already lives in pinned host memory -- what
         `play_games` hands its callback -- is read by the first kernel over PCIe where it is (its address travels in a
         pinned word, c4_f32_batch); any other array takes one copy into a device buffer first."""
-        import ctypes as C
-        import numpy as np
-
-        from ._lib import check
-
         x = np.ascontiguousarray(x, dtype=np.float32)
         b = int(x.shape[0])
         if b == 0:
             return np.zeros((0, 7), np.float32), np.zeros((0,), np.float32), np.zeros((0,), np.float32)
-        if not (self.hip_tower and self.device.type == "cuda"):
+        if self.chain.np_planes is None:
             lp, q = self.forward(torch.from_numpy(x).to(self.device))
             lp, q = lp.float().cpu().numpy(), q.float().cpu().numpy()
             return np.ascontiguousarray(lp), np.ascontiguousarray(q[:, 0]), np.ascontiguousarray(q[:, 1])
@@ -493,38 +531,27 @@ class InferenceNet:
             return self._forward_numpy_locked(x, b, bucket)
 
     def _forward_numpy_locked(self, x, b: int, bucket: int):
-        import ctypes as C
-        import numpy as np
-
-        from ._lib import check
-
+        ch = self.chain
         st = getattr(self, "_np", None)
         if st is None or st["cap"] < bucket:
             cap = max(2048, 1 << (bucket - 1).bit_length())
             st = self._np = {"cap": cap, "graphs": {}, "stream": torch.cuda.Stream(device=self.device),
                              "in": torch.zeros((cap, 2, 6, 7), dtype=torch.float32, device=self.device),
-                             "planes": None if self.f32 else torch.zeros((cap, 2, 6, 7), dtype=torch.bfloat16, device=self.device),
                              "slot": torch.zeros(2, dtype=torch.int64).pin_memory(),      # c4_f32_batch {data, n_boards}
                              "h_lp": torch.zeros((cap, 7), dtype=torch.float32).pin_memory(),
-                             "h_q": torch.zeros((cap, 2), dtype=torch.float32).pin_memory()}
+                             "h_q": torch.zeros((cap, 2), dtype=torch.float32).pin_memory(),
+                             "planes": torch.zeros((cap, 2, 6, 7), dtype=torch.bfloat16, device=self.device) if ch.np_converts else None}
             st["slot_np"] = st["slot"].numpy()
         stream = st["stream"]
-        xt = torch.from_numpy(x) if x.flags.writeable else None
-        direct = xt is not None and x.ctypes.data % 16 == 0 and xt.is_pinned()
         with torch.cuda.stream(stream):
             g = st["graphs"].get(bucket)
             if g is None:
                 from .session import CAPTURE_ERROR_MODE
 
                 def body():
-                    if self.f32:     # the f32 chain reads the f32 positions themselves (rows b .. bucket - 1: earlier batches, unread)
-                        self.forward(st["in"][:bucket], out_logprobs=st["h_lp"][:bucket], out_q=st["h_q"][:bucket], latency=True)
-                        return
-                    check(self._L.c4_planes_from_f32(C.c_void_p(st["slot"].data_ptr()), None, 0, C.c_void_p(st["planes"].data_ptr()), bucket,
-                                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
                     # the output kernel's stores go to pinned host memory: no copy after it.  latency=True: a host round
                     # trip, this forward has the chip to itself (an argument of the call, not a mutation of the shared net)
-                    self.forward(st["planes"][:bucket], out_logprobs=st["h_lp"][:bucket], out_q=st["h_q"][:bucket], latency=True)
+                    self.forward(ch.np_planes(st, bucket), out_logprobs=st["h_lp"][:bucket], out_q=st["h_q"][:bucket], latency=True)
 
                 st["slot_np"][0], st["slot_np"][1] = st["in"].data_ptr(), 0     # warm-up and capture run on empty boards
                 for _ in range(2):      # warm-up outside the capture (lazy module loads, LDS opt-ins)
@@ -534,12 +561,10 @@ class InferenceNet:
                 with torch.cuda.graph(g, stream=stream, capture_error_mode=CAPTURE_ERROR_MODE):
                     body()
                 st["graphs"][bucket] = g
-            if self.f32:
-                st["in"][:b].copy_(xt if xt is not None else torch.from_numpy(x.copy()), non_blocking=True)
-            elif direct:
+            if ch.np_converts and x.flags.writeable and x.ctypes.data % 16 == 0 and torch.from_numpy(x).is_pinned():
                 st["slot_np"][0] = x.ctypes.data
             else:
-                st["in"][:b].copy_(torch.from_numpy(x), non_blocking=True)
+                st["in"][:b].copy_(torch.from_numpy(x if x.flags.writeable else x.copy()), non_blocking=True)
                 st["slot_np"][0] = st["in"].data_ptr()
             st["slot_np"][1] = b
             g.replay()
@@ -582,38 +607,12 @@ class InferenceNet:
     use_loader_waves = True   # False: no wave-specialised (loader-wavefront) forms anywhere (A/B)
     wide_tiles_r5 = True      # False: round 4's choice for the 2F-wide layer between 1 025 and 1 728 rows (A/B)
 
-    def _pick_config(self, m: int, n: int, k: int, latency: Optional[bool] = None) -> int:
-        return self._alone_config(m, n, k, latency)
-
     def _linear_relu(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
                      latency: Optional[bool] = None) -> torch.Tensor:
-        """ReLU(x W^T + b): the hand-written MFMA GEMM, or (gemm="hipblaslt") the library's with the bias
-        and ReLU in its epilogue where available."""
-        if self.f32:
-            from ._lib import check
-            import ctypes as C
-
-            assert x.stride(1) == 1 and w.is_contiguous()
-            m, n, k = x.shape[0], w.shape[0], w.shape[1]
-            y = out if out is not None else torch.empty((m, n), dtype=torch.float32, device=self.device)
-            check(self._L.c4_linear_f32(C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(y.data_ptr()),
-                                        m, n, k, x.stride(0), y.stride(0), 1, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-            return y
-        if self.gemm == "hip":
-            from ._lib import check
-            import ctypes as C
-
-            assert x.stride(1) == 1 and w.is_contiguous()
-            m, n, k = x.shape[0], w.shape[0], w.shape[1]
-            y = out if out is not None else torch.empty((m, n), dtype=torch.bfloat16, device=self.device)
-            check(self._L.c4_linear_bf16(C.c_void_p(x.data_ptr()), C.c_void_p(w.data_ptr()), C.c_void_p(self._bias32[b.data_ptr()].data_ptr()),
-                                         C.c_void_p(y.data_ptr()), m, n, k, x.stride(0), y.stride(0), 1,
-                                         self.gemm_config[0 if n > k else 1] or self._pick_config(m, n, k, latency),
-                                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-            return y
-        if self.fused_epilogue:
-            return torch._addmm_activation(b, x, w.t(), use_gelu=False)
-        return F.relu(F.linear(x, w, b))
+        """ReLU(x W^T + b): one hidden layer on this net's chain.  The tile configuration (c4_linear_bf16's; the other GEMMs have
+        none) is `gemm_config`'s or, where that says automatic, `_alone_config`'s."""
+        n, k = w.shape
+        return self.chain.linear_relu(x, w, b, out, self.gemm_config[0 if n > k else 1] or self._alone_config(x.shape[0], n, k, latency))
 
     __call__ = forward
 
@@ -648,3 +647,4 @@ def flops_per_leaf(cfg: ModelConfig) -> int:
     pol = (cfg.n_policy_layers - 1) * 2 * f * f + 2 * 7 * f
     val = (cfg.n_value_layers - 1) * 2 * f * f + 2 * 2 * f
     return conv + pol + val
+
