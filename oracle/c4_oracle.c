@@ -11,6 +11,7 @@
 #endif
 #include "c4_oracle.h"
 
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -672,7 +673,8 @@ struct c4o_game {
   int mv_col[C4O_MAX_MOVES + 1];
   int error;
   float dir_alpha, dir_eps; /* Dirichlet root noise (extension); eps == 0 disables */
-  uint64_t last_select_levels;
+  uint64_t last_select_levels; /* levels of the last select_new_leaf: the depth of g->leaf below the root */
+  int prev_step_moved;         /* the last c4o_game_step call made a move */
   c4o_counters ctr;
 };
 
@@ -834,8 +836,12 @@ int c4o_game_on_received_policy(c4o_game* g, const float* logprobs_in, float q_p
   c4o_pos leaf_pos = g->nodes[g->leaf].pos;
   float tq_pen, tq_nopen;
   g->ctr.sims++;
+  const uint64_t depth = g->last_select_levels; /* the leaf this simulation backs up from sits this many levels below the root */
+  if (depth > g->ctr.max_depth) g->ctr.max_depth = depth;
+  if (depth >= 16) g->ctr.sims_deep++;
   if (c4o_terminal_value(&leaf_pos, c_ply_penalty, &tq_pen, &tq_nopen) != C4O_NOT_TERMINAL) {
     int is_root = (g->leaf == g->root);
+    if (depth >= 16) g->ctr.sims_deep_terminal++;
     if (is_root) g->ctr.sims_terminal_root++;
     backpropagate_value(g, tq_pen, tq_nopen, !is_root);
     select_new_leaf(g, c_exploration);
@@ -977,7 +983,7 @@ int c4o_game_step(c4o_game* g, const float* logprobs7, float q_pen, float q_nope
                   uint64_t n_mcts_iterations, float c_exploration, float c_ply_penalty) {
   int e = c4o_game_on_received_policy(g, logprobs7, q_pen, q_nopen, c_exploration, c_ply_penalty);
   if (e) return -e;
-  if (c4o_game_root_visit_count(g) < n_mcts_iterations) return 0; /* self_play.rs:283-286 */
+  if (c4o_game_root_visit_count(g) < n_mcts_iterations) { g->prev_step_moved = 0; return 0; } /* self_play.rs:283-286 */
   g->ctr.select_levels_discarded += g->last_select_levels;
   c4o_pos root_pos = g->nodes[g->root].pos;
   if (c4o_terminal_state(&root_pos) == C4O_NOT_TERMINAL) {
@@ -985,8 +991,11 @@ int c4o_game_step(c4o_game* g, const float* logprobs7, float q_pen, float q_nope
     float temperature = (ply < 4) ? 4.0f : (ply < 8) ? 2.0f : 1.0f;
     e = c4o_game_make_random_move(g, c_exploration, temperature);
     if (e) return -e;
+    if (g->prev_step_moved) g->ctr.moves_without_search++; /* the child already had its n visits when it became the root */
+    g->prev_step_moved = 1;
     return 0;
   }
+  g->prev_step_moved = 0;
   return 1; /* self_play.rs:302-308 */
 }
 
@@ -1042,6 +1051,53 @@ int c4o_eval_hash(void* ctx, uint64_t model_id, int n, const float* planes, floa
     c4o_pos p;
     planes_to_pos(planes + (size_t)84 * i, &p);
     c4o_hash_eval_pos(p.mask, p.value, lp + 7 * i, qp + i, qn + i);
+  }
+  return 0;
+}
+
+/* Sharp evaluator: the hash evaluator in the regime of a trained network.  Logits = the hash logits x 2^k (exact in f32: the
+ * hash logits are multiples of 1/8 below 4 in magnitude), so the tree's own masked softmax underflows legal priors to subnormals
+ * and to exact zeros and the search goes deep; q_mode 1 ("sat") answers sign(q) in {-1, 0, +1}, as a saturated tanh does;
+ * ties != 0 gives the positions with h % 8 == 0 seven equal logits (0), so that the last-maximum rule decides at depth.
+ * No transcendental: CPU and GPU twins agree bit for bit.  The ctx also tallies what the answers do to the priors. */
+void c4o_sharp_eval_pos(uint64_t mask, uint64_t value, int k, int q_mode, int ties, float* logits7, float* q_pen, float* q_nopen) {
+  c4o_hash_eval_pos(mask, value, logits7, q_pen, q_nopen);
+  int64_t v0 = (int64_t)(value & 0x1FFFFF), v1 = (int64_t)(value >> 21);
+  int64_t m0 = (int64_t)(mask & 0x1FFFFF), m1 = (int64_t)(mask >> 21);
+  int64_t h = (v0 * 1000003 + v1 * 998244353 + m0 * 19260817 + m1 * 1000000007) % 2147483647;
+  const float scale = (float)((uint64_t)1 << k);
+  for (int c = 0; c < 7; c++) logits7[c] = (ties && h % 8 == 0) ? 0.0f : logits7[c] * scale;
+  if (q_mode == 1) {
+    *q_pen = (float)((*q_pen > 0.0f) - (*q_pen < 0.0f));
+    *q_nopen = (float)((*q_nopen > 0.0f) - (*q_nopen < 0.0f));
+  }
+}
+
+int c4o_eval_sharp(void* ctx, uint64_t model_id, int n, const float* planes, float* lp, float* qp, float* qn) {
+  (void)model_id;
+  c4o_eval_sharp_ctx* s = (c4o_eval_sharp_ctx*)ctx;
+  if (!s || s->k < 0 || s->k > 16) return 1;
+  for (int i = 0; i < n; i++) {
+    c4o_pos p;
+    planes_to_pos(planes + (size_t)84 * i, &p);
+    c4o_sharp_eval_pos(p.mask, p.value, s->k, s->q_mode, s->ties, lp + 7 * i, qp + i, qn + i);
+    /* what the tree makes of the row (mcts.rs:83-108): masked softmax; a terminal leaf's answer is ignored */
+    s->rows++;
+    if (c4o_terminal_state(&p) != C4O_NOT_TERMINAL) continue;
+    float lg[7], pr[7];
+    memcpy(lg, lp + 7 * i, sizeof lg);
+    c4o_mask_policy(&p, lg);
+    if (c4o_softmax7(lg, pr)) continue;
+    s->rows_used++;
+    unsigned legal = c4o_legal_mask(&p);
+    int zero = 0, sub = 0;
+    for (int c = 0; c < 7; c++) {
+      if (!((legal >> c) & 1)) continue;
+      if (pr[c] == 0.0f) zero = 1;
+      else if (pr[c] < FLT_MIN) sub = 1;
+    }
+    s->rows_zero_prior += (uint64_t)zero;
+    s->rows_subnormal_prior += (uint64_t)sub;
   }
   return 0;
 }
@@ -1237,6 +1293,9 @@ int c4o_self_play(const c4o_game_metadata* reqs, uint64_t n_games, int max_nn_ba
     st.tree.select_levels += c.select_levels; st.tree.select_levels_discarded += c.select_levels_discarded;
     st.tree.backup_nodes += c.backup_nodes;
     st.tree.expansions += c.expansions; st.tree.nodes_created += c.nodes_created; st.tree.moves += c.moves;
+    st.tree.sims_deep += c.sims_deep; st.tree.sims_deep_terminal += c.sims_deep_terminal;
+    if (c.max_depth > st.tree.max_depth) st.tree.max_depth = c.max_depth;
+    st.tree.moves_without_search += c.moves_without_search;
     c4o_game_free(games[i]);
   }
   out_offsets[n_games] = off;
@@ -1572,6 +1631,9 @@ int c4o_self_play_async(const c4o_game_metadata* reqs, uint64_t n_games, int max
     st.tree.select_levels += c.select_levels; st.tree.select_levels_discarded += c.select_levels_discarded;
     st.tree.backup_nodes += c.backup_nodes;
     st.tree.expansions += c.expansions; st.tree.nodes_created += c.nodes_created; st.tree.moves += c.moves;
+    st.tree.sims_deep += c.sims_deep; st.tree.sims_deep_terminal += c.sims_deep_terminal;
+    if (c.max_depth > st.tree.max_depth) st.tree.max_depth = c.max_depth;
+    st.tree.moves_without_search += c.moves_without_search;
     c4o_game_free(a.games[i]);
   }
   out_offsets[n_games] = off;

@@ -125,6 +125,10 @@ typedef struct {
   uint64_t expansions;         /* expand_leaf calls that created children */
   uint64_t nodes_created;
   uint64_t moves;
+  uint64_t sims_deep;          /* simulations whose backed-up path has leaf depth >= 16 (levels below the root) */
+  uint64_t sims_deep_terminal; /* of which: the leaf was terminal */
+  uint64_t max_depth;          /* largest leaf depth of a simulation (c4o_selfplay_stats: the maximum over the games) */
+  uint64_t moves_without_search; /* moves made on the c4o_game_step call directly after a move: the new root already had n visits */
 } c4o_counters;
 
 c4o_game* c4o_game_new(const c4o_pos* start, uint64_t game_id, uint64_t player0_id, uint64_t player1_id); /* mcts.rs:48-56 */
@@ -204,6 +208,13 @@ int c4o_eval_hash(void* ctx, uint64_t model_id, int n, const float* planes,
                   float* logprobs, float* q_pen, float* q_nopen);    /* integer hash of the position (parity tier T1) */
 /* the integer-hash evaluator on a position (shared definition with the GPU tests) */
 void c4o_hash_eval_pos(uint64_t mask, uint64_t value, float* logits7, float* q_pen, float* q_nopen);
+/* c4o_eval_sharp's ctx: hash logits x 2^k; q_mode 0 = the hash q, 1 = sign(q); ties != 0 = seven equal logits where h % 8 == 0.
+ * The evaluator adds to the tallies: rows answered; of those, rows_used = the non-terminal ones (the tree ignores the answer
+ * for a terminal leaf, mcts.rs:92-98); of those, the rows whose masked c4o_softmax7 gives a LEGAL move a prior of exactly 0 / a
+ * subnormal prior. */
+typedef struct { int32_t k, q_mode, ties, pad; uint64_t rows, rows_used, rows_zero_prior, rows_subnormal_prior; } c4o_eval_sharp_ctx;
+int c4o_eval_sharp(void* ctx, uint64_t model_id, int n, const float* planes, float* lp, float* qp, float* qn);
+void c4o_sharp_eval_pos(uint64_t mask, uint64_t value, int k, int q_mode, int ties, float* logits7, float* q_pen, float* q_nopen);
 
 #ifdef __cplusplus
 }

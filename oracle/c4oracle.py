@@ -59,7 +59,8 @@ class CSample(C.Structure):
 
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
-        "sims", "sims_terminal_root", "select_levels", "select_levels_discarded", "backup_nodes", "expansions", "nodes_created", "moves")]
+        "sims", "sims_terminal_root", "select_levels", "select_levels_discarded", "backup_nodes", "expansions", "nodes_created", "moves",
+        "sims_deep", "sims_deep_terminal", "max_depth", "moves_without_search")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -77,6 +78,13 @@ class SelfPlayStats(C.Structure):
 class EvalTableCtx(C.Structure):
     _fields_ = [("n", C.c_uint64), ("mask", C.c_void_p), ("value", C.c_void_p), ("out", C.c_void_p)]
 
+
+class EvalSharpCtx(C.Structure):
+    _fields_ = [("k", C.c_int32), ("q_mode", C.c_int32), ("ties", C.c_int32), ("pad", C.c_int32),
+                ("rows", C.c_uint64), ("rows_used", C.c_uint64), ("rows_zero_prior", C.c_uint64), ("rows_subnormal_prior", C.c_uint64)]
+
+
+SHARP_Q_MODES = {"hash": 0, "sat": 1}
 
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_float),
                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float))
@@ -149,6 +157,8 @@ def lib() -> C.CDLL:
         "c4o_self_play_async": (C.c_int, [P(GameMetadataC), C.c_uint64, C.c_int, C.c_uint64, C.c_float, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_int, P(CSample), P(C.c_uint64), P(SelfPlayStats)]),
         "c4o_hash_eval_pos": (None, [C.c_uint64, C.c_uint64, f32p, f32p, f32p]),
+        "c4o_sharp_eval_pos": (None, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p]),
+        "c4o_eval_sharp": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, f32p, f32p, f32p, f32p]),
         "c4o_set_thread_pinning": (None, [C.c_int]),
     }
     for name, (res, args) in sig.items():
@@ -323,6 +333,19 @@ def hash_eval_pos(mask: int, value: int):
     return np.array(lg[:], dtype=np.float32), a.value, b.value
 
 
+def sharp_eval_batch(planes: np.ndarray, k: int, q_mode: str, ties: bool):
+    """c4o_eval_sharp on float32[B, 2, 6, 7] -> (logits[B, 7], q_pen[B], q_nopen[B], tallies dict)."""
+    x = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1, 2, 6, 7)
+    n = len(x)
+    lp, qp, qn = np.zeros((n, 7), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    ctx = EvalSharpCtx(int(k), SHARP_Q_MODES[q_mode], int(bool(ties)))
+    f32p = C.POINTER(C.c_float)
+    if lib().c4o_eval_sharp(C.cast(C.pointer(ctx), C.c_void_p), 0, n, x.ctypes.data_as(f32p), lp.ctypes.data_as(f32p),
+                            qp.ctypes.data_as(f32p), qn.ctypes.data_as(f32p)):
+        raise ValueError("c4o_eval_sharp refused its parameters")
+    return lp, qp, qn, {"rows": int(ctx.rows), "rows_used": int(ctx.rows_used), "rows_zero_prior": int(ctx.rows_zero_prior), "rows_subnormal_prior": int(ctx.rows_subnormal_prior)}
+
+
 class Game:
     """One MctsGame (mcts.rs:27-32)."""
 
@@ -426,7 +449,9 @@ def self_play(reqs: Sequence[Tuple[int, int, int]], max_nn_batch_size: int, n_mc
               dirichlet: Tuple[float, float] = (0.0, 0.0), topology: str = "lockstep"):
     """Oracle restatement of self_play.rs:39-129.
 
-    `evaluator`: "uniform" | "zeros" | "hash" (built-in C evaluators) or a Python callable
+    `evaluator`: "uniform" | "zeros" | "hash" (built-in C evaluators), ("sharp", k, q_mode, ties) (c4o_eval_sharp: hash logits
+    x 2^k, q_mode "hash" | "sat", ties; the stats then carry rows / rows_used / rows_zero_prior / rows_subnormal_prior, what the answers did to
+    the priors), ("table", mask, value, out) (c4o_eval_table) or a Python callable
     with the reference callback signature cb(model_id, float32[B,2,6,7]) ->
     (float32[B,7], float32[B], float32[B]) (pybridge.rs:170-198).
     Returns (dict game_id -> [SampleRec], stats dict).  Result order is per reqs order.
@@ -448,6 +473,11 @@ def self_play(reqs: Sequence[Tuple[int, int, int]], max_nn_batch_size: int, n_mc
     ctx = None
     if isinstance(evaluator, str):
         fn = C.cast(getattr(L, {"uniform": "c4o_eval_uniform", "zeros": "c4o_eval_zeros", "hash": "c4o_eval_hash"}[evaluator]), C.c_void_p)
+    elif isinstance(evaluator, tuple) and evaluator[0] == "sharp":
+        _tag, s_k, s_q, s_ties = evaluator
+        keep = EvalSharpCtx(int(s_k), SHARP_Q_MODES[s_q], int(bool(s_ties)))
+        ctx = C.cast(C.pointer(keep), C.c_void_p)
+        fn = C.cast(L.c4o_eval_sharp, C.c_void_p)
     elif isinstance(evaluator, tuple) and evaluator[0] == "table":
         # ("table", mask uint64[n], value uint64[n], out float32[n, 9]) sorted by (mask, value): c4o_eval_table, tier T3 at full size
         _tag, t_mask, t_value, t_out = evaluator
@@ -492,4 +522,6 @@ def self_play(reqs: Sequence[Tuple[int, int, int]], max_nn_batch_size: int, n_mc
         res[gid] = [SampleRec.from_c(out[j]) for j in range(offs[i], offs[i + 1])]
     st = {"n_games": int(stats.n_games), "n_samples": int(stats.n_samples), "nn_calls": int(stats.nn_calls),
           "nn_positions": int(stats.nn_positions), **stats.tree.as_dict()}
+    if isinstance(keep, EvalSharpCtx):
+        st.update(rows=int(keep.rows), rows_used=int(keep.rows_used), rows_zero_prior=int(keep.rows_zero_prior), rows_subnormal_prior=int(keep.rows_subnormal_prior))
     return res, st

@@ -63,6 +63,138 @@ class GraphSafeHashEval:
         return out_logprobs, out_q
 
 
+def _hash_h_np(planes: np.ndarray):
+    mask, value = planes_to_pos_np(planes)
+    mask = mask.astype(np.int64)
+    value = value.astype(np.int64)
+    return ((value & 0x1FFFFF) * P1 + (value >> 21) * P2 + (mask & 0x1FFFFF) * P3 + (mask >> 21) * P4) % MOD
+
+
+def sharp_eval_np(k: int, q_mode: str = "hash", ties: bool = False):
+    """numpy twin of the oracle's c4o_eval_sharp as a reference-signature callback: the hash evaluator in the regime of a trained
+    network.  Logits = the hash logits x 2^k (exact in f32; raw logits, the tree's own masked softmax does the underflowing to
+    subnormal and zero priors), q_mode "sat" answers sign(q) in {-1, 0, +1}, ties gives the positions with h % 8 == 0 seven
+    equal logits (0) so that the last-maximum rule decides at depth.  No transcendental anywhere: every twin agrees bit for bit."""
+    assert q_mode in ("hash", "sat") and 0 <= int(k) <= 16
+
+    def cb(_model_id, planes: np.ndarray):
+        logits, qp, qn = hash_eval_np(_model_id, planes)
+        logits = logits * np.float32(2.0 ** int(k))
+        if ties:
+            logits = np.where((_hash_h_np(planes) % 8 == 0)[:, None], np.float32(0.0), logits)
+        if q_mode == "sat":
+            qp, qn = np.sign(qp), np.sign(qn)
+        return (np.ascontiguousarray(logits, dtype=np.float32), np.ascontiguousarray(qp, dtype=np.float32),
+                np.ascontiguousarray(qn, dtype=np.float32))
+
+    return cb
+
+
+def sharp_eval_torch(k: int, q_mode: str = "hash", ties: bool = False):
+    """torch twin of sharp_eval_np (device evaluator): planes[G,2,6,7] -> (logits[G,7] f32, q[G,2] f32)."""
+    assert q_mode in ("hash", "sat") and 0 <= int(k) <= 16
+
+    def ev(planes):
+        import torch
+
+        logits, q = hash_eval_torch(planes)
+        logits = logits * float(2.0 ** int(k))
+        if ties:
+            g = planes.shape[0]
+            b = (planes.reshape(g, 2, 42) != 0).to(torch.int64)
+            w = (torch.ones(42, dtype=torch.int64, device=planes.device) << torch.arange(42, dtype=torch.int64, device=planes.device))
+            value = (b[:, 0, :] * w).sum(dim=1)
+            mask = value | (b[:, 1, :] * w).sum(dim=1)
+            h = ((value & 0x1FFFFF) * P1 + (value >> 21) * P2 + (mask & 0x1FFFFF) * P3 + (mask >> 21) * P4) % MOD
+            logits = torch.where((h % 8 == 0)[:, None], torch.zeros_like(logits), logits)
+        if q_mode == "sat":
+            q = torch.sign(q)
+        return logits, q
+
+    return ev
+
+
+class GraphSafeSharpEval(GraphSafeHashEval):
+    """sharp_eval_torch as a graph-safe device evaluator (see GraphSafeHashEval)."""
+
+    def __init__(self, k: int, q_mode: str = "hash", ties: bool = False):
+        self.ev = sharp_eval_torch(k, q_mode, ties)
+
+    def __call__(self, planes, out_logprobs=None, out_q=None):
+        lp, q = self.ev(planes)
+        if out_logprobs is None:
+            return lp, q
+        out_logprobs.copy_(lp)
+        out_q.copy_(q)
+        return out_logprobs, out_q
+
+
+def sharp_model(blocks: int, channels: int, k: int, seed: int = 1337):
+    """A default-initialised ConnectFourNet (4 policy / 2 value layers) sharpened into the regime of a trained one: the policy
+    output layer (weight and bias) x 2^k, the value output layer x 2^(k // 2) and its bias + 0.5 afterwards.  Powers of two keep
+    the bf16 weights exact scalings of the unsharpened network's; the priors turn peaked and tanh saturates, so the search goes
+    deep (tests/test_sharp_regime.py asserts how deep)."""
+    import torch
+    from c4a0_amd.nn import ConnectFourNet, ModelConfig
+
+    torch.manual_seed(seed)
+    model = ConnectFourNet(ModelConfig(blocks, channels, 4, 2)).eval()
+    pol, val = model.fc_policy[-2], model.fc_value[-2]
+    with torch.no_grad():
+        pol.weight.mul_(2.0 ** k)
+        pol.bias.mul_(2.0 ** k)
+        val.weight.mul_(2.0 ** (k // 2))
+        val.bias.mul_(2.0 ** (k // 2)).add_(0.5)
+    return model
+
+
+# sharp_model's k in the GPU tests.  Measured on the oracle with the f32 PyTorch model as its evaluator (tests/test_sharp_regime.py
+# asserts the first): 4 x 32, n = 100, 32 games: 15.7 % of the simulations at depth >= 16 with k = 8, 29 % with 9, 38 % with 10;
+# 8 x 64, n = 800, 8 games: 8.2 %, 28 %, 32 %.  8 meets the CPU floor of 10 % but leaves the 8 x 64 shape near the 3 % the GPU
+# replay must show with bf16 answers; 9 clears both with room.
+SHARP_MODEL_K = 9
+
+# The evaluators of the sharp regime, (k, q_mode, ties), and with which exploration constant they are played.
+SHARP_EVALS = {
+    "k4": ((4, "hash", False), 6.6),
+    "k4sat": ((4, "sat", False), 6.6),
+    "k5sat": ((5, "sat", False), 1.4),
+    "k4ties": ((4, "sat", True), 6.6),
+}
+
+# T1 matrix of the sharp regime: tests/test_gpu_sharp_regime.py plays each job on the device against the oracle, and
+# tests/test_sharp_regime.py holds the oracle alone, on exactly these jobs (ids, n, c, evaluator, Dirichlet), to the coverage
+# floors.  (name, evaluator, n, planes, first id, options); every job is N_SHARP_GAMES games on N_SHARP_SLOTS slots, so every
+# slot is refilled.  The tie evaluator spreads a search over seven equal priors at one position in eight and reaches the floors
+# of the deep path at n = 400 only; it runs at 24 and 400.  Dirichlet noise (0.3, 0.25) gives every child of a root a share of its
+# visits, so a move straight after a move becomes rare (1-3 % of the moves at n >= 100, under that floor): the noisy jobs run at
+# n = 24, where the noise meets the zero and subnormal priors; below the root it changes nothing.  The reclaimed arenas run under the
+# k = 5, c = 1.4 evaluator: it expands 250-740 nodes per game, several halves' worth, where k = 4 reuses its tree (95 per game).
+N_SHARP_GAMES, N_SHARP_SLOTS = 512, 256
+SHARP_JOBS = [
+    ("k4-n100-f32-eager", "k4", 100, "f32", 10_000, {}),
+    ("k4sat-n100-bf16-graph", "k4sat", 100, "bf16", 20_000, {"graph": 8}),
+    ("k5sat-n100-f32-graph", "k5sat", 100, "f32", 30_000, {"graph": 2}),
+    ("k4sat-n24-f32-dirichlet", "k4sat", 24, "f32", 35_000, {"dirichlet": (0.3, 0.25)}),
+    ("k4ties-n400-bf16-eager", "k4ties", 400, "bf16", 40_000, {}),
+    ("k4sat-n400-f32-tiny-cache", "k4sat", 400, "f32", 50_000, {"cache": (1024, 8)}),
+    ("k4-n24-bf16-roomy-cache", "k4", 24, "bf16", 60_000, {"cache": (1 << 16, 0)}),
+    ("k4sat-n24-bf16-dirichlet-cache", "k4sat", 24, "bf16", 70_000, {"dirichlet": (0.3, 0.25), "cache": (1 << 16, 0)}),
+    ("k5sat-n100-f32-reclaim1", "k5sat", 100, "f32", 80_000, {"reclaim": 1}),
+    ("k5sat-n400-bf16-reclaim3-graph", "k5sat", 400, "bf16", 90_000, {"reclaim": 3, "graph": 4}),
+    ("k4ties-n24-f32-graph", "k4ties", 24, "f32", 100_000, {"graph": 16}),
+    ("k5sat-n24-f32-tiny-cache", "k5sat", 24, "f32", 110_000, {"cache": (1024, 8)}),
+    ("k4-n400-f32-graph", "k4", 400, "f32", 120_000, {"graph": 8}),
+    ("k4sat-n100-callback-gather", "k4sat", 100, "f32", 130_000, {"callback": True}),
+]
+
+
+def sharp_job_reqs(first_id: int, n_games: int = N_SHARP_GAMES):
+    """ids include 0 (seed 0 on every move), colliding seeds 43 * 42 == 42 * 43 (mcts.rs:215) and 64-bit patterns"""
+    ids = [0, 42, 43, 1 << 40, (1 << 64) - 1] + list(range(first_id, first_id + n_games - 5))
+    return [(g, 0, 0) for g in ids]
+
+
 def uniform_eval_torch(planes):
     """self_play.rs:391-403 UniformEvalPos on device."""
     import torch

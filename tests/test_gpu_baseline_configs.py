@@ -117,7 +117,7 @@ def _keys_to_positions(keys):
     return mask, value
 
 
-def _run_logging_every_row(net, ids, n_slots, n_iter, dirichlet=None):
+def _run_logging_every_row(net, ids, n_slots, n_iter, dirichlet=None, planes_dtype=torch.bfloat16):
     """One eager session; at EVERY step the key of every slot's leaf and the evaluator's answer for it are logged on the device.
     Returns (records, counts, counters, table) with table = (mask, value, out[n, 9]) sorted by (mask, value): what the evaluator
     said for every distinct position it was shown during the whole job -- after checking that it said the SAME bits every time it
@@ -127,7 +127,7 @@ def _run_logging_every_row(net, ids, n_slots, n_iter, dirichlet=None):
     from c4a0_amd.session import DeviceSession
 
     dev = torch.device("cuda:0")
-    s = DeviceSession(n_slots, n_iter, 6.6, 0.01, device=dev, planes_dtype=torch.bfloat16)
+    s = DeviceSession(n_slots, n_iter, 6.6, 0.01, device=dev, planes_dtype=planes_dtype)
     s.set_games([(g, 0, 0) for g in ids])
     if dirichlet is not None:
         s.set_dirichlet(*dirichlet)
@@ -203,7 +203,7 @@ def _hash_run(ids, n_slots, n_iter):
 # ---------------------------------------------------------------------------------------------
 def test_config4_4096_games_n800_hash_evaluator_structure_and_oracle_subset():
     """BASELINE config 4's tree shape: 4 096 concurrent games, n_mcts_iterations = 800 (deep trees,
-    the largest arenas, paths beyond 16 levels)."""
+    the largest arenas, paths beyond 16 levels: the oracle's own counters say so for the replayed subset)."""
     from oracle import c4oracle as O
     from tests.helpers import oracle_samples_by_game
     from tests.test_gpu_full_size import _check_structure
@@ -215,10 +215,12 @@ def test_config4_4096_games_n800_hash_evaluator_structure_and_oracle_subset():
     _check_structure(recs, counts, ids)
     assert ctr["sims"] / n > 7 * 300
     sub = sorted(np.random.default_rng(4).choice(ids, 1024, replace=False).tolist())   # round 6: 1 024 games through the oracle (128 in round 5, 16 before): 10 M simulations
-    want, _ = O.self_play([(g, 0, 0) for g in sub], 4096, n_iter, 6.6, 0.01, "hash", n_threads=max(2, min(16, os.cpu_count() or 2)), topology="async")
+    want, ost = O.self_play([(g, 0, 0) for g in sub], 4096, n_iter, 6.6, 0.01, "hash", n_threads=max(2, min(16, os.cpu_count() or 2)), topology="async")
     assert _subset(recs, sub) == oracle_samples_by_game(want)
+    assert ost["max_depth"] > 16 and ost["sims_deep"] > 0          # "paths beyond 16 levels": a few per thousand simulations (tests/test_sharp_regime.py)
     from tests.helpers import evidence
-    evidence(f"config 4 tree shape (4 096 games, n = 800, hash evaluator): {len(recs)} samples structurally checked, {len(sub)} games == oracle bit for bit")
+    evidence(f"config 4 tree shape (4 096 games, n = 800, hash evaluator): {len(recs)} samples structurally checked, {len(sub)} games == oracle bit for bit; "
+             f"{ost['sims_deep']} of {ost['sims']} simulations at depth >= 16 (max {ost['max_depth']})")
 
 
 def test_config4_4096_games_n800_8x64_network_t3_replay():
