@@ -548,6 +548,11 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
 #define C4_STAMP_TRIP1(i, force) do { if (sim == 0) C4_STAMP(i, force); } while (0)
 #pragma clang loop unroll(disable)
     for (uint32_t sim = 0; sim < max_sims; sim++) {
+      // A terminal leaf at depth 0 is a terminal START position (a move into a terminal position closes the game in the launch that
+      // makes it).  The reference gives such a root its n simulations, none of which can change the game's one sample
+      // (self_play.rs:283-308, mcts.rs:271-313): as after a move into a terminal position, the game is closed now and the
+      // simulations are counted as skipped.  (C4_FLAG_NO_MOVES, the reference's run_mcts, keeps searching such a root.)
+      const bool term_start = term != 0 && depth == 0 && !(p.flags & C4_FLAG_NO_MOVES);
       // ---------------- on_received_policy: terminal value or expansion -------------------
       float v_pen, v_nopen;
       if (term) {
@@ -617,8 +622,8 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
         }
       }
       root_n = shfl_u32(root_n, gbase + 4);
-      c_sims += 1;
-      c_K += depth + 1;
+      c_sims += term_start ? 0u : 1u;
+      c_K += term_start ? 0u : depth + 1;
       // The stores above are read back below through other lanes of THIS wavefront.  A wavefront's
       // vector-memory instructions reach the cache in program order, so a later load of the same
       // address returns the stored bytes without waiting for the store's acknowledgement: only the
@@ -629,10 +634,10 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
 
       // ---------------- gate: self_play.rs:283-308 ------------------------------------------
       bool finished = false;
-      if (root_n >= p.n_iter && !(p.flags & C4_FLAG_NO_MOVES)) {
+      if ((root_n >= p.n_iter && !(p.flags & C4_FLAG_NO_MOVES)) || term_start) {
         const size_t rec0 = (size_t)ordinal * C4_MAX_SAMPLES_PER_GAME;
-        uint32_t rterm = c4::terminal_state(rmask, rvalue);  // non-zero only for a terminal START position
-        uint32_t retained = p.n_iter;
+        uint32_t rterm = term_start ? term : 0u;             // a root is terminal only as a terminal START position
+        uint32_t retained = term_start ? 0u : p.n_iter;
         if (!rterm) {
           // root_policy (mcts.rs:396-412): child visit counts / their sum
           const uint4 re = load_block_lane(blocks, root_block, sub);

@@ -110,7 +110,8 @@ typedef struct {
   uint64_t expansions;      /* sum of E: expand_leaf calls that created children (mcts.rs:114-132) */
   uint64_t moves;           /* make_random_move calls (mcts.rs:214-222) */
   uint64_t games_done;
-  uint64_t ref_skipped_sims;/* terminal-root sims the reference would still run (self_play.rs:283-301) */
+  uint64_t ref_skipped_sims;/* terminal-root sims the reference would still run (self_play.rs:283-301): after a move
+                               into a terminal position, and all n of a terminal start position */
   uint64_t samples;
   uint64_t games_started;
   uint64_t step_kernel_ns;  /* device-clock time inside c4_session_step's kernel, summed over launches:
@@ -145,8 +146,14 @@ int c4_trim_cached_memory(void);
 
 /* `reqs: Vec<GameMetadata>` of self_play() (self_play.rs:41).  Copies the list to the device,
  * allocates the sample store (43 records per game), resets queue and counters.
- * start_masks/start_values (host arrays, may be NULL = empty board, self_play.rs:56) give
- * MctsGame::new_from_pos positions (mcts.rs:48) for tests.  Synchronises the stream. */
+ * start_masks/start_values (host arrays of n_games, may be NULL = empty board, self_play.rs:56) give
+ * every game its start position, MctsGame::new_from_pos (mcts.rs:48-56): ANY position, terminal ones
+ * included, indexed like reqs.  Whole games from it are the reference's, sample for sample: the
+ * temperature, the ply penalty and the leaf's model follow the ply of the position, the move seed, the
+ * Dirichlet key, the record index and the sign of each sample's q the moves THIS game has made
+ * (mcts.rs:215, 271-313).  A game whose start is terminal yields its one sample in the first step that
+ * sees it; the n simulations the reference spends on such a root are counted in ref_skipped_sims
+ * (with C4_FLAG_NO_MOVES they are run, as mcts.rs' run_mcts runs them).  Synchronises the stream. */
 int c4_session_set_games(c4_session* s, const c4_game_metadata* reqs, uint64_t n_games,
                          const uint64_t* start_masks, const uint64_t* start_values);
 

@@ -1307,6 +1307,56 @@ int c4o_self_play(const c4o_game_metadata* reqs, uint64_t n_games, int max_nn_ba
   return rc;
 }
 
+/* Whole games from given start positions (MctsGame::new_from_pos, mcts.rs:48-56): every game is played ALONE to its end through
+ * c4o_game_step, one evaluator row per job (self_play.rs:268-323), with the model of c4o_game_leaf_model_id.  A game's trajectory
+ * depends on the answers for its own leaves alone, so with starts == NULL the samples are c4o_self_play's. */
+int c4o_play_from(const c4o_game_metadata* reqs, const c4o_pos* starts, uint64_t n_games,
+                  uint64_t n_mcts_iterations, float c_exploration, float c_ply_penalty,
+                  c4o_eval_fn eval, void* eval_ctx, float dirichlet_alpha, float dirichlet_epsilon,
+                  c4o_sample* out_samples, uint64_t* out_offsets, c4o_selfplay_stats* stats) {
+  int rc = C4O_OK;
+  c4o_selfplay_stats st;
+  memset(&st, 0, sizeof st);
+  st.n_games = n_games;
+  uint64_t off = 0;
+  const c4o_pos empty = {0, 0};
+  for (uint64_t i = 0; i < n_games; i++) {
+    out_offsets[i] = off;
+    if (rc != C4O_OK) continue;
+    c4o_game* g = c4o_game_new(starts ? &starts[i] : &empty, reqs[i].game_id, reqs[i].player0_id, reqs[i].player1_id);
+    c4o_game_set_dirichlet(g, dirichlet_alpha, dirichlet_epsilon);
+    for (;;) {
+      c4o_pos leaf;
+      float planes[C4O_BUF_LEN], lp[7], qp, qn;
+      c4o_game_leaf_pos(g, &leaf);
+      c4o_write_planes(&leaf, planes);
+      st.nn_calls++;
+      st.nn_positions++;
+      if (eval(eval_ctx, c4o_game_leaf_model_id(g), 1, planes, lp, &qp, &qn) != 0) { rc = C4O_ERR_DEGENERATE_POLICY; break; }
+      const int status = c4o_game_step(g, lp, qp, qn, n_mcts_iterations, c_exploration, c_ply_penalty);
+      if (status < 0) { rc = -status; break; }
+      if (status == 1) {
+        const int n = c4o_game_to_result(g, c_ply_penalty, out_samples + off, 43);
+        if (n < 0) rc = -n; else off += (uint64_t)n;
+        break;
+      }
+    }
+    const c4o_counters c = g->ctr;
+    st.tree.sims += c.sims; st.tree.sims_terminal_root += c.sims_terminal_root;
+    st.tree.select_levels += c.select_levels; st.tree.select_levels_discarded += c.select_levels_discarded;
+    st.tree.backup_nodes += c.backup_nodes;
+    st.tree.expansions += c.expansions; st.tree.nodes_created += c.nodes_created; st.tree.moves += c.moves;
+    st.tree.sims_deep += c.sims_deep; st.tree.sims_deep_terminal += c.sims_deep_terminal;
+    if (c.max_depth > st.tree.max_depth) st.tree.max_depth = c.max_depth;
+    st.tree.moves_without_search += c.moves_without_search;
+    c4o_game_free(g);
+  }
+  out_offsets[n_games] = off;
+  st.n_samples = off;
+  if (stats) *stats = st;
+  return rc;
+}
+
 /* ------------------------------------------------------------------------------------------
  * self_play in the REFERENCE'S THREAD TOPOLOGY -- rust/src/self_play.rs:39-129: one NN thread
  * (NNThread, :196-237) and n_threads - 1 MCTS worker threads (MctsThread, :268-323) exchanging

@@ -183,6 +183,15 @@ int c4o_self_play(const c4o_game_metadata* reqs, uint64_t n_games, int max_nn_ba
                   c4o_eval_fn eval, void* eval_ctx, int n_threads,
                   c4o_sample* out_samples, uint64_t* out_offsets, c4o_selfplay_stats* stats);
 
+/* Whole games from START POSITIONS: game i starts at starts[i] (MctsGame::new_from_pos, mcts.rs:48-56; any position, terminal
+ * included; NULL = the empty board) and is played alone to its end with c4o_game_step, one evaluator row per job.  Samples,
+ * offsets and statistics as c4o_self_play writes them (nn_calls = nn_positions = evaluator rows); Dirichlet noise as
+ * c4o_game_set_dirichlet takes it, (0, 0) = off.  With starts == NULL every game's samples equal c4o_self_play's. */
+int c4o_play_from(const c4o_game_metadata* reqs, const c4o_pos* starts, uint64_t n_games,
+                  uint64_t n_mcts_iterations, float c_exploration, float c_ply_penalty,
+                  c4o_eval_fn eval, void* eval_ctx, float dirichlet_alpha, float dirichlet_epsilon,
+                  c4o_sample* out_samples, uint64_t* out_offsets, c4o_selfplay_stats* stats);
+
 /* The same job in the REFERENCE'S THREAD TOPOLOGY (self_play.rs:60-106): the calling thread is the
  * NN thread (NNThread::loop_until_close, :196-237), n_threads - 1 worker threads are the MctsThreads
  * (:268-323), games travel over two queues, network evaluation and tree work overlap.  Same samples

@@ -156,6 +156,8 @@ def lib() -> C.CDLL:
                                     C.c_void_p, C.c_void_p, C.c_int, P(CSample), P(C.c_uint64), P(SelfPlayStats)]),
         "c4o_self_play_async": (C.c_int, [P(GameMetadataC), C.c_uint64, C.c_int, C.c_uint64, C.c_float, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_int, P(CSample), P(C.c_uint64), P(SelfPlayStats)]),
+        "c4o_play_from": (C.c_int, [P(GameMetadataC), P(Pos), C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                    C.c_float, C.c_float, P(CSample), P(C.c_uint64), P(SelfPlayStats)]),
         "c4o_hash_eval_pos": (None, [C.c_uint64, C.c_uint64, f32p, f32p, f32p]),
         "c4o_sharp_eval_pos": (None, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p]),
         "c4o_eval_sharp": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, f32p, f32p, f32p, f32p]),
@@ -381,6 +383,9 @@ class Game:
         self._L.c4o_game_leaf_pos(self._g, C.byref(p))
         return p
 
+    def leaf_model_id(self) -> int:
+        return int(self._L.c4o_game_leaf_model_id(self._g))
+
     def root_visit_count(self) -> int:
         return self._L.c4o_game_root_visit_count(self._g)
 
@@ -444,33 +449,11 @@ def run_mcts(pos: Pos, n_iterations: int, c_exploration=4.0, c_ply_penalty=0.01,
 NpEval = Callable[[int, np.ndarray], Tuple[np.ndarray, np.ndarray, np.ndarray]]
 
 
-def self_play(reqs: Sequence[Tuple[int, int, int]], max_nn_batch_size: int, n_mcts_iterations: int,
-              c_exploration: float, c_ply_penalty: float, evaluator="uniform", n_threads: int = 1,
-              dirichlet: Tuple[float, float] = (0.0, 0.0), topology: str = "lockstep"):
-    """Oracle restatement of self_play.rs:39-129.
-
-    `evaluator`: "uniform" | "zeros" | "hash" (built-in C evaluators), ("sharp", k, q_mode, ties) (c4o_eval_sharp: hash logits
-    x 2^k, q_mode "hash" | "sat", ties; the stats then carry rows / rows_used / rows_zero_prior / rows_subnormal_prior, what the answers did to
-    the priors), ("table", mask, value, out) (c4o_eval_table) or a Python callable
-    with the reference callback signature cb(model_id, float32[B,2,6,7]) ->
-    (float32[B,7], float32[B], float32[B]) (pybridge.rs:170-198).
-    Returns (dict game_id -> [SampleRec], stats dict).  Result order is per reqs order.
-
-    topology="async" runs the reference's thread topology (c4o_self_play_async): this thread is the
-    NN thread, n_threads - 1 worker threads run the MCTS jobs, evaluation and tree work overlap.
-    Same samples either way.
-    """
+def _resolve_evaluator(evaluator, err: List[BaseException]):
+    """`evaluator` as self_play documents it -> (c4o_eval_fn as a void pointer, its ctx, what must stay alive during the call);
+    an exception raised by a Python callable is appended to `err`."""
     L = lib()
-    n = len(reqs)
-    arr = (GameMetadataC * max(1, n))()
-    for i, (gid, p0, p1) in enumerate(reqs):
-        arr[i] = GameMetadataC(gid, p0, p1)
-    out = (CSample * (43 * max(1, n)))()
-    offs = (C.c_uint64 * (n + 1))()
-    stats = SelfPlayStats()
-    keep = None
-    err: List[BaseException] = []
-    ctx = None
+    keep, ctx = None, None
     if isinstance(evaluator, str):
         fn = C.cast(getattr(L, {"uniform": "c4o_eval_uniform", "zeros": "c4o_eval_zeros", "hash": "c4o_eval_hash"}[evaluator]), C.c_void_p)
     elif isinstance(evaluator, tuple) and evaluator[0] == "sharp":
@@ -505,6 +488,46 @@ def self_play(reqs: Sequence[Tuple[int, int, int]], max_nn_batch_size: int, n_mc
 
         keep = EVAL_FN(_cb)
         fn = C.cast(keep, C.c_void_p)
+    return fn, ctx, keep
+
+
+def _collect(reqs, out, offs, stats, keep):
+    res = {}
+    for i, (gid, _p0, _p1) in enumerate(reqs):
+        res[gid] = [SampleRec.from_c(out[j]) for j in range(offs[i], offs[i + 1])]
+    st = {"n_games": int(stats.n_games), "n_samples": int(stats.n_samples), "nn_calls": int(stats.nn_calls),
+          "nn_positions": int(stats.nn_positions), **stats.tree.as_dict()}
+    if isinstance(keep, EvalSharpCtx):
+        st.update(rows=int(keep.rows), rows_used=int(keep.rows_used), rows_zero_prior=int(keep.rows_zero_prior), rows_subnormal_prior=int(keep.rows_subnormal_prior))
+    return res, st
+
+
+def self_play(reqs: Sequence[Tuple[int, int, int]], max_nn_batch_size: int, n_mcts_iterations: int,
+              c_exploration: float, c_ply_penalty: float, evaluator="uniform", n_threads: int = 1,
+              dirichlet: Tuple[float, float] = (0.0, 0.0), topology: str = "lockstep"):
+    """Oracle restatement of self_play.rs:39-129.
+
+    `evaluator`: "uniform" | "zeros" | "hash" (built-in C evaluators), ("sharp", k, q_mode, ties) (c4o_eval_sharp: hash logits
+    x 2^k, q_mode "hash" | "sat", ties; the stats then carry rows / rows_used / rows_zero_prior / rows_subnormal_prior, what the answers did to
+    the priors), ("table", mask, value, out) (c4o_eval_table) or a Python callable
+    with the reference callback signature cb(model_id, float32[B,2,6,7]) ->
+    (float32[B,7], float32[B], float32[B]) (pybridge.rs:170-198).
+    Returns (dict game_id -> [SampleRec], stats dict).  Result order is per reqs order.
+
+    topology="async" runs the reference's thread topology (c4o_self_play_async): this thread is the
+    NN thread, n_threads - 1 worker threads run the MCTS jobs, evaluation and tree work overlap.
+    Same samples either way.
+    """
+    L = lib()
+    n = len(reqs)
+    arr = (GameMetadataC * max(1, n))()
+    for i, (gid, p0, p1) in enumerate(reqs):
+        arr[i] = GameMetadataC(gid, p0, p1)
+    out = (CSample * (43 * max(1, n)))()
+    offs = (C.c_uint64 * (n + 1))()
+    stats = SelfPlayStats()
+    err: List[BaseException] = []
+    fn, ctx, keep = _resolve_evaluator(evaluator, err)
     L.c4o_self_play_set_dirichlet(float(dirichlet[0]), float(dirichlet[1]))  # extension; (0, 0) = off
     if topology not in ("lockstep", "async"):
         raise ValueError("topology must be 'lockstep' or 'async'")
@@ -516,12 +539,35 @@ def self_play(reqs: Sequence[Tuple[int, int, int]], max_nn_batch_size: int, n_mc
         raise err[0]
     if rc:
         raise RuntimeError(f"oracle self_play error {rc}")
-    res = {}
-    for i, (gid, _p0, _p1) in enumerate(reqs):
-        res.setdefault(gid, [])
-        res[gid] = [SampleRec.from_c(out[j]) for j in range(offs[i], offs[i + 1])]
-    st = {"n_games": int(stats.n_games), "n_samples": int(stats.n_samples), "nn_calls": int(stats.nn_calls),
-          "nn_positions": int(stats.nn_positions), **stats.tree.as_dict()}
-    if isinstance(keep, EvalSharpCtx):
-        st.update(rows=int(keep.rows), rows_used=int(keep.rows_used), rows_zero_prior=int(keep.rows_zero_prior), rows_subnormal_prior=int(keep.rows_subnormal_prior))
-    return res, st
+    return _collect(reqs, out, offs, stats, keep)
+
+
+def play_from(reqs: Sequence[Tuple[int, int, int]], starts: Optional[Sequence[Tuple[int, int]]], n_mcts_iterations: int,
+              c_exploration: float, c_ply_penalty: float, evaluator="uniform", dirichlet: Tuple[float, float] = (0.0, 0.0)):
+    """Whole games from start positions (c4o_play_from): game i starts at starts[i] = (mask, value) -- MctsGame::new_from_pos,
+    mcts.rs:48-56; any position, terminal included; None = every game from the empty board -- and is played alone to its end with
+    c4o_game_step.  `evaluator` and the result as for self_play (samples per game id: ids must be distinct)."""
+    L = lib()
+    n = len(reqs)
+    arr = (GameMetadataC * max(1, n))()
+    for i, (gid, p0, p1) in enumerate(reqs):
+        arr[i] = GameMetadataC(gid, p0, p1)
+    pos = None
+    if starts is not None:
+        if len(starts) != n:
+            raise ValueError("starts must match reqs")
+        pos = (Pos * max(1, n))()
+        for i, (m, v) in enumerate(starts):
+            pos[i] = Pos(int(m), int(v))
+    out = (CSample * (43 * max(1, n)))()
+    offs = (C.c_uint64 * (n + 1))()
+    stats = SelfPlayStats()
+    err: List[BaseException] = []
+    fn, ctx, keep = _resolve_evaluator(evaluator, err)
+    rc = L.c4o_play_from(arr, pos, n, n_mcts_iterations, c_exploration, c_ply_penalty, fn, ctx, float(dirichlet[0]), float(dirichlet[1]),
+                         out, offs, C.byref(stats))
+    if err:
+        raise err[0]
+    if rc:
+        raise RuntimeError(f"oracle play_from error {rc}")
+    return _collect(reqs, out, offs, stats, keep)

@@ -195,6 +195,82 @@ def sharp_job_reqs(first_id: int, n_games: int = N_SHARP_GAMES):
     return [(g, 0, 0) for g in ids]
 
 
+# ------------------------------------------------------------------------------------------------ games from start positions
+# The job of tests/test_start_positions.py (the oracle alone: floors, twin mutants) and tests/test_gpu_start_positions.py (the
+# device against the oracle): whole games from given positions, where popcount(root) -- temperature, ply penalty, leaf model --
+# and the moves the game has recorded -- move seed, Dirichlet key, record index, sign of every sample's q -- are different numbers.
+START_SEED = 11
+START_BANDS = ((1, 8), (8, 20), (20, 30), (30, 36), (36, 42))   # plies [lo, hi) of the random part
+START_PER_BAND = 96
+N_START_SLOTS = 128
+# tests/test_oracle_rules.py test_pos_ops_edge_cases' drawn board, move by move
+DRAWN_LINE = [0, 1, 2, 3, 4, 5] * 3 + [5, 4, 3, 2, 1, 0] * 3 + [6] * 6
+_START_JOB = {}
+
+
+def start_job(seed: int = START_SEED):
+    """(reqs, starts, part): 495 games, shuffled so that terminal, late and early starts interleave; part[i] = "random" | "line"
+    | "won", where game i's start comes from.
+    Random part: 96 positions from each ply band of START_BANDS, the first of O.random_positions_np(200_000, seed) that fall into
+    it (terminal ones, kind 2, included as they come).  Constructed part: DRAWN_LINE cut k = 0..6 moves short, each twice (k = 0:
+    a terminal draw; k >= 1: one legal column, drawn after k moves, samples' q alternating 0.0 / -0.0), and Pos(0b1111, 0b1111), a
+    terminal start of kind 1.  Ids: 0, 42, 43, 1 << 40, 2^64 - 1 (mcts.rs:215: seed 0 on every move, colliding seeds 43 * 42 ==
+    42 * 43, 64-bit patterns) on five of the random games, then distinct ones; the players' ids differ (mcts.rs:70-76)."""
+    if seed in _START_JOB:
+        return _START_JOB[seed]
+    from oracle import c4oracle as O
+
+    mask, value = O.random_positions_np(200_000, seed)
+    ply = np.array([bin(int(m)).count("1") for m in mask])
+    starts, part = [], []
+    for lo, hi in START_BANDS:
+        idx = np.flatnonzero((ply >= lo) & (ply < hi))[:START_PER_BAND]
+        assert len(idx) == START_PER_BAND, (lo, hi, len(idx))
+        starts += [(int(mask[i]), int(value[i])) for i in idx]
+        part += ["random"] * START_PER_BAND
+    for k in range(7):
+        starts += [O.from_moves(DRAWN_LINE[: 42 - k]).key()] * 2
+        part += ["line"] * 2
+    starts.append((0b1111, 0b1111))
+    part.append("won")
+    ids = [0, 42, 43, 1 << 40, (1 << 64) - 1]
+    ids = ids + [7_000_000 + 3 * i for i in range(len(starts) - len(ids))]
+    order = np.random.default_rng(seed).permutation(len(starts))
+    starts, part = [starts[i] for i in order], [part[i] for i in order]
+    reqs = [(g, 11, (1 << 63) + 5) for g in ids]   # ids stay in list order: the special ones land on shuffled positions
+    _START_JOB[seed] = (reqs, starts, part)
+    return _START_JOB[seed]
+
+
+# The evaluators the job is played under: name -> (the oracle's evaluator, c_exploration, (k, q_mode, ties) of the sharp twins or
+# None = the hash evaluator).
+START_EVALS = {
+    "hash": ("hash", 6.6, None),
+    "k4sat": (("sharp",) + SHARP_EVALS["k4sat"][0], SHARP_EVALS["k4sat"][1], SHARP_EVALS["k4sat"][0]),
+    "k5sat": (("sharp",) + SHARP_EVALS["k5sat"][0], SHARP_EVALS["k5sat"][1], SHARP_EVALS["k5sat"][0]),
+}
+# (evaluator, n): the settings of the T1 matrix below; tests/test_start_positions.py holds the oracle to the floors under each
+START_SETTINGS = [("hash", 24), ("hash", 100), ("k4sat", 24), ("k5sat", 100)]
+# T1 matrix of tests/test_gpu_start_positions.py: (name, evaluator, n, planes, options), every job the 495 games on N_START_SLOTS
+# slots, so that three starts in four arrive through the refill.
+START_JOBS = [
+    ("hash-n24-f32-eager", "hash", 24, "f32", {}),
+    ("hash-n100-bf16-eager", "hash", 100, "bf16", {}),
+    ("k4sat-n24-bf16-graph2", "k4sat", 24, "bf16", {"graph": 2}),
+    ("k5sat-n100-f32-graph8", "k5sat", 100, "f32", {"graph": 8}),
+    ("hash-n100-f32-tiny-cache", "hash", 100, "f32", {"cache": (1024, 8)}),
+    ("k4sat-n24-bf16-roomy-cache", "k4sat", 24, "bf16", {"cache": (1 << 16, 0)}),
+    ("hash-n24-f32-dirichlet", "hash", 24, "f32", {"dirichlet": (0.3, 0.25)}),
+    ("k4sat-n24-bf16-dirichlet-cache-graph", "k4sat", 24, "bf16", {"dirichlet": (0.3, 0.25), "cache": (1 << 16, 0), "graph": 4}),
+    ("k5sat-n100-f32-reclaim1", "k5sat", 100, "f32", {"reclaim": 1}),
+    ("hash-n100-bf16-reclaim3-graph", "hash", 100, "bf16", {"reclaim": 3, "graph": 4}),
+    ("hash-n24-f32-compact", "hash", 24, "f32", {"compact": 5}),
+    ("k5sat-n100-bf16-compact", "k5sat", 100, "bf16", {"compact": 7}),
+    ("hash-n24-gather", "hash", 24, "f32", {"gather": True}),
+    ("k4sat-n24-gather-dirichlet", "k4sat", 24, "f32", {"gather": True, "dirichlet": (0.3, 0.25)}),
+]
+
+
 def uniform_eval_torch(planes):
     """self_play.rs:391-403 UniformEvalPos on device."""
     import torch

@@ -117,18 +117,19 @@ def _keys_to_positions(keys):
     return mask, value
 
 
-def _run_logging_every_row(net, ids, n_slots, n_iter, dirichlet=None, planes_dtype=torch.bfloat16):
+def _run_logging_every_row(net, ids, n_slots, n_iter, dirichlet=None, planes_dtype=torch.bfloat16, starts=None):
     """One eager session; at EVERY step the key of every slot's leaf and the evaluator's answer for it are logged on the device.
     Returns (records, counts, counters, table) with table = (mask, value, out[n, 9]) sorted by (mask, value): what the evaluator
     said for every distinct position it was shown during the whole job -- after checking that it said the SAME bits every time it
-    was shown a position again (the evaluator is a function of the position), over every row of every step."""
+    was shown a position again (the evaluator is a function of the position), over every row of every step.
+    starts: the games' start positions (DeviceSession.set_games), None = the empty board."""
     import ctypes as C
     from c4a0_amd._lib import check
     from c4a0_amd.session import DeviceSession
 
     dev = torch.device("cuda:0")
     s = DeviceSession(n_slots, n_iter, 6.6, 0.01, device=dev, planes_dtype=planes_dtype)
-    s.set_games([(g, 0, 0) for g in ids])
+    s.set_games([(g, 0, 0) for g in ids], starts)
     if dirichlet is not None:
         s.set_dirichlet(*dirichlet)
     log_k, log_o = [], []
