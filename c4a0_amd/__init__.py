@@ -11,9 +11,12 @@ from .results import GameMetadata, GameResult, PlayGamesResult, Sample  # noqa: 
 
 
 def __getattr__(name):  # torch / the HIP library are loaded on first use of the entry points
-    if name in ("play_games", "run_tui", "DeviceCallback", "trim_cached_memory"):
+    if name in ("play_games", "search_positions", "run_tui", "DeviceCallback", "trim_cached_memory"):
         from . import api
         return getattr(api, name)
+    if name == "SearchResult":
+        from .results import SearchResult
+        return SearchResult
     if name == "play_games_native":
         from .native import play_games_native
         return play_games_native

@@ -20,8 +20,9 @@ FLAG_NO_MOVES = 1
 FLAG_ONE_SIM_PER_STEP = 2
 FLAG_RECLAIM = 4          # include/c4a0_hip.h C4_FLAG_RECLAIM: the tree arena is reclaimed while a game is played
 FLAG_NO_RECLAIM = 8       # ... never, also where the default sizing would
+FLAG_SEARCH = 16          # include/c4a0_hip.h C4_FLAG_SEARCH: every request is one search of its start position (one record), not a game
 MAX_SAMPLES_PER_GAME = 43
-ABI_VERSION = 11   # include/c4a0_hip.h C4_ABI_VERSION: the signatures below are that version's
+ABI_VERSION = 12   # include/c4a0_hip.h C4_ABI_VERSION: the signatures below are that version's
 STRUCT_LAYOUT_SINCE = 7   # the ABI version that last changed a structure's layout (c4_config.reclaim_period, c4_counters.reclaim_*)
 
 
@@ -119,6 +120,8 @@ SIGNATURES = {
     "c4_play_games_cancel": (None, []),
     "c4_play_games_bf16": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_float, C.c_float, _P(NetworkBf16), _P(PlayOptions), _vp, _vp, C.c_uint64,
                                      _P(C.c_uint64), _P(Counters), _P(PlayPhases)]),
+    "c4_search_positions_bf16": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_float, C.c_float, _P(NetworkBf16), _P(PlayOptions), _vp, C.c_uint64,
+                                           _P(Counters), _P(PlayPhases)]),
     "c4_cbor_to_records": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64)]),
     "c4_session_leaf_keys": (C.c_int, [_vp, _vp]),
     "c4_session_unique_leaves": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),

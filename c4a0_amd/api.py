@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
-from .results import GameMetadata, PlayGamesResult, results_from_records
+from .results import GameMetadata, PlayGamesResult, SearchResult, results_from_records
 from .session import DeviceEvaluator, DeviceSession
 
 # Games advanced in lock-step per round when the caller does not say (`resident_games=`).  Two forces (MI355X, BASELINE config 2's
@@ -39,7 +39,7 @@ DEFAULT_RESIDENT_GAMES = 4096
 MAX_DEFAULT_RESIDENT_GAMES = 16384
 
 
-def default_resident_games(n_games: int, n_mcts_iterations: int, graph_safe: bool, device=None) -> int:
+def default_resident_games(n_games: int, n_mcts_iterations: int, graph_safe: bool, device=None, search: bool = False) -> int:
     if n_games <= DEFAULT_RESIDENT_GAMES or not graph_safe:   # callback / multi-model modes: a host round trip per round, rows are not the limit
         return min(n_games, DEFAULT_RESIDENT_GAMES)
     want = DEFAULT_RESIDENT_GAMES
@@ -47,7 +47,7 @@ def default_resident_games(n_games: int, n_mcts_iterations: int, graph_safe: boo
         want *= 2
     # arena bytes per slot (include/c4a0_hip.h c4_config.blocks_per_slot): 43 n + 8 blocks of 128 bytes, or two reclaimed halves above n = 1 000
     n = max(1, n_mcts_iterations)
-    per_slot = 128 * ((43 * n + 8) if n <= 1000 else 2 * (5 * n // 2 + 554))
+    per_slot = 128 * ((n + 8) if search else (43 * n + 8) if n <= 1000 else 2 * (5 * n // 2 + 554))   # (a search: one block per simulation)
     try:
         free, _total = torch.cuda.mem_get_info(device)
         while want > DEFAULT_RESIDENT_GAMES and want * per_slot > free // 4:
@@ -325,7 +325,8 @@ def _play(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_ply_penal
 
 def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_ply_penalty, py_eval_pos_cb, evaluator, device=None,
                  resident_games=None, planes_dtype=None, blocks_per_slot=0, stats=None, dirichlet=None, concurrent_sessions=None,
-                 eval_cache_entries=0, on_device=False, reclaim=None, reclaim_period=0, host_loop=None):
+                 eval_cache_entries=0, on_device=False, reclaim=None, reclaim_period=0, host_loop=None, start_positions=None, search=False):
+    """search=True (search_positions): request i is ONE search of start_positions[i] (uint64[n, 2]) and yields one record."""
     from .session import run_sessions
 
     if not isinstance(reqs, np.ndarray):
@@ -338,14 +339,14 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
             from .native import run_native
             return run_native(reqs, n_mcts_iterations, c_exploration, c_ply_penalty, evaluator, resident_games=resident_games, concurrent_sessions=concurrent_sessions,
                               blocks_per_slot=blocks_per_slot, reclaim=reclaim, reclaim_period=reclaim_period, dirichlet=dirichlet,
-                              eval_cache_entries=eval_cache_entries, stats=stats, on_device=on_device)
+                              eval_cache_entries=eval_cache_entries, stats=stats, on_device=on_device, start_positions=start_positions, search=search)
         if host_loop == "native":
             raise TypeError(f"host_loop='native': {why}")
     multi = evaluator is not None and isinstance(evaluator, dict)
     if planes_dtype is None:   # hand a bf16 network bf16 planes (0/1 are exact): no conversion kernel per step
         planes_dtype = torch.bfloat16 if getattr(evaluator, "dtype", None) == torch.bfloat16 else torch.float32
     graph_safe = evaluator is not None and not multi and getattr(evaluator, "graph_safe", False)
-    n_slots = min(len(reqs), int(resident_games) if resident_games else default_resident_games(len(reqs), int(n_mcts_iterations), graph_safe, device))
+    n_slots = min(len(reqs), int(resident_games) if resident_games else default_resident_games(len(reqs), int(n_mcts_iterations), graph_safe, device, search))
     # Device evaluators that are pure device code: the resident games are split over sessions that run
     # concurrently on their own streams (session.run_sessions), two by default when each half still
     # fills the GEMMs.  Which session plays a game does not change its samples.
@@ -367,7 +368,7 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
     # graphs while the job is long -- judged by the rounds it will take, ~15 moves x n simulations per generation of games -- and,
     # for two paired sessions, short ones from the first narrowing of the tail on, where the graph is captured again anyway
     # (session._run_pair).  The reference's default job (1 700 games, n = 1 400: 37 000 rounds, one session) replays 32.
-    est_rounds = -(-len(reqs) // max(1, n_slots)) * 15 * max(1, int(n_mcts_iterations))
+    est_rounds = -(-len(reqs) // max(1, n_slots)) * (1 if search else 15) * max(1, int(n_mcts_iterations))   # (a search: n simulations, no moves)
     if not graph_safe:
         steps_per_graph = tail_steps_per_graph = 0
     elif parts == 2:
@@ -388,9 +389,9 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
             mine = reqs[p::parts]
             slots = min(len(mine), (n_slots + parts - 1 - p) // parts)
             s = DeviceSession(max(1, slots), n_mcts_iterations, c_exploration, c_ply_penalty, device=device,
-                              planes_dtype=planes_dtype, blocks_per_slot=blocks_per_slot, reclaim=reclaim, reclaim_period=reclaim_period)
+                              planes_dtype=planes_dtype, blocks_per_slot=blocks_per_slot, reclaim=reclaim, reclaim_period=reclaim_period, search=search)
             sessions.append(s)
-            s.set_games(mine)
+            s.set_games(mine, None if start_positions is None else start_positions[p::parts])
             if dirichlet is not None:   # extension: (alpha, epsilon) root noise; the reference has none
                 s.set_dirichlet(*dirichlet)
             if eval_cache_entries:      # extension: evaluation cache, each session keeps its own table
@@ -445,6 +446,63 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
         for s in sessions:
             s.close()
     return recs, counts
+
+
+_CELLS = (1 << 42) - 1
+
+
+def _positions_array(positions) -> np.ndarray:
+    """uint64[P, 2] (mask, value) of `positions`, validated in numpy: the bitboards of c4r.rs:13-17 that a game can show."""
+    if isinstance(positions, np.ndarray):
+        if positions.ndim != 2 or positions.shape[1] != 2 or positions.dtype.kind not in "ui":
+            raise TypeError("positions must be a sequence of (mask, value) or an integer array of shape [P, 2]")
+        if positions.dtype.kind == "i" and bool((positions < 0).any()):
+            raise ValueError(f"position {int(np.flatnonzero((positions < 0).any(axis=1))[0])}: negative bitboard")
+        pos = np.ascontiguousarray(positions, dtype=np.uint64)
+    else:
+        try:
+            pos = np.array([(int(m), int(v)) for m, v in positions], dtype=np.uint64).reshape(-1, 2)
+        except (TypeError, OverflowError):
+            raise TypeError("positions must be a sequence of (mask, value) pairs of unsigned 64-bit integers") from None
+    mask, value = pos[:, 0], pos[:, 1]
+    for bad, what in (((mask | value) & ~np.uint64(_CELLS)) != 0, "bits outside the 42 cells"), ((value & ~mask) != 0, "value has bits outside mask"), \
+                     ((((mask >> np.uint64(7)) & ~mask) & np.uint64(_CELLS)) != 0, "a stone above an empty cell"):
+        if bool(bad.any()):
+            raise ValueError(f"position {int(np.flatnonzero(bad)[0])}: {what}")
+    return pos
+
+
+def search_positions(positions, n_mcts_iterations: int, c_exploration: float, c_ply_penalty: float, *, evaluator: Optional[DeviceEvaluator] = None,
+                     device=None, resident_games: Optional[int] = None, planes_dtype: Optional[torch.dtype] = None, blocks_per_slot: int = 0,
+                     concurrent_sessions: Optional[int] = None, host_loop: Optional[str] = None, stats: Optional[dict] = None,
+                     on_device: bool = False):
+    """Search every position of `positions` -- a sequence of (mask, value), or a uint64[P, 2] array -- with `n_mcts_iterations`
+    simulations from the position as root, and return the root policies and root q values as a `SearchResult` in the order given
+    (with on_device=True: the packed records, a uint8[P, 64] tensor that never left the GPU).
+
+    What the reference does one position at a time with `MctsGame::new_from_pos` and `n` rounds of leaf -> evaluator ->
+    `on_received_policy` (mcts.rs:48-56, the run_mcts helper of mcts.rs:469-485, `InteractivePlay`, interactive_play.rs:33, 57):
+    here all positions are one job of the self-play schedule -- sessions, HIP graphs, refill, narrowing, the library's own loop for
+    an unmodified bf16 `InferenceNet` (`host_loop` as for `play_games`) -- in which a "game" ends at its first gate with one record.
+    Any position a game can show is accepted, terminal ones included (searched like the reference searches them).  `evaluator` is
+    one device evaluator as `play_games(evaluator=)` takes it; no numpy callbacks, no per-model dicts, no noise, no cache."""
+    pos = _positions_array(positions)
+    if not (1 <= int(n_mcts_iterations) <= 32200):
+        raise ValueError("n_mcts_iterations must be between 1 and 32 200")
+    if evaluator is None or isinstance(evaluator, dict) or not callable(evaluator):
+        raise TypeError("search_positions needs ONE device evaluator (evaluator=callable on device tensors, e.g. c4a0_amd.nn.InferenceNet)")
+    if len(pos) == 0:
+        if on_device:
+            return torch.empty((0, 64), dtype=torch.uint8, device=device if device is not None else getattr(evaluator, "device", "cuda"))
+        return SearchResult(np.zeros(0, dtype=SearchResult.DTYPE))
+    ids = np.zeros((len(pos), 3), dtype=np.uint64)
+    ids[:, 0] = np.arange(len(pos), dtype=np.uint64)          # requests (game_id = i, 0, 0)
+    with _JOB_LOCK:   # one job at a time per process, games or searches (see _play)
+        recs, counts = _play_locked(ids, 1, int(n_mcts_iterations), c_exploration, c_ply_penalty, None, evaluator, device=device, resident_games=resident_games,
+                                    planes_dtype=planes_dtype, blocks_per_slot=blocks_per_slot, stats=stats, concurrent_sessions=concurrent_sessions,
+                                    on_device=on_device, host_loop=host_loop, start_positions=pos, search=True)
+    assert len(recs) == len(pos) and bool((np.asarray(counts) == 1).all())
+    return recs if on_device else SearchResult(recs)
 
 
 def trim_cached_memory() -> None:

@@ -39,7 +39,7 @@ using c4host::fail;
 #define HIP_OK(expr)                                                                                         \
   do {                                                                                                       \
     hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return fail(C4_ERR_HIP, std::string("c4_play_games_bf16: " #expr ": ") + hipGetErrorString(e_)); \
+    if (e_ != hipSuccess) return fail(C4_ERR_HIP, std::string(t_who + ": " #expr ": ") + hipGetErrorString(e_)); \
   } while (0)
 #define C4_TRY(expr)                \
   do {                              \
@@ -47,6 +47,7 @@ using c4host::fail;
     if (rc_ != C4_OK) return rc_;   \
   } while (0)
 
+thread_local std::string t_who = "c4_play_games_bf16";   // the entry point this thread's job came in through: prefix of its messages
 std::atomic<uint32_t> g_cancel_requested{0};   // c4_play_games_cancel -> the running job's loop
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -163,11 +164,11 @@ int capture(Job& j, const c4_network_bf16& net, uint32_t rounds, bool fused) {
   if (rc != C4_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
   if (he != hipSuccess || he_end != hipSuccess) {
     if (graph) (void)hipGraphDestroy(graph);
-    return fail(C4_ERR_HIP, std::string("c4_play_games_bf16: graph capture: ") + hipGetErrorString(he != hipSuccess ? he : he_end));
+    return fail(C4_ERR_HIP, std::string(t_who + ": graph capture: ") + hipGetErrorString(he != hipSuccess ? he : he_end));
   }
   he = hipGraphInstantiate(&j.exec, graph, nullptr, nullptr, 0);
   (void)hipGraphDestroy(graph);
-  if (he != hipSuccess) { j.exec = nullptr; return fail(C4_ERR_HIP, std::string("c4_play_games_bf16: hipGraphInstantiate: ") + hipGetErrorString(he)); }
+  if (he != hipSuccess) { j.exec = nullptr; return fail(C4_ERR_HIP, std::string(t_who + ": hipGraphInstantiate: ") + hipGetErrorString(he)); }
   return C4_OK;
 }
 
@@ -191,29 +192,31 @@ __global__ __launch_bounds__(64) void k_merge_samples(MergeArgs a, const unsigne
 
 }  // namespace
 
-extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games, uint32_t n_mcts_iterations, float c_exploration,
-                                  float c_ply_penalty, const c4_network_bf16* net, const c4_play_options* opt_in, uint32_t* counts_host,
-                                  c4_sample_rec* records_host, uint64_t records_cap, uint64_t* n_records, c4_counters* totals,
-                                  c4_play_phases* phases) {
-  if (!net || !n_records || (n_games && (!reqs || !counts_host))) return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: null argument");
+// The job of both entry points below: `reqs` played on the network, as whole games (search == false; start_masks / start_values NULL:
+// every game starts on the empty board) or as one search per request from its start position (search == true: C4_FLAG_SEARCH sessions,
+// everything after the gate works on 1-record "games").
+static int run_job(const c4_game_metadata* reqs, const uint64_t* start_masks, const uint64_t* start_values, bool search, uint64_t n_games,
+                   uint32_t n_mcts_iterations, float c_exploration, float c_ply_penalty, const c4_network_bf16* net, const c4_play_options* opt_in,
+                   uint32_t* counts_host, c4_sample_rec* records_host, uint64_t records_cap, uint64_t* n_records, c4_counters* totals,
+                   c4_play_phases* phases) {
   c4_play_options opt{};
   if (opt_in) opt = *opt_in;
   *n_records = 0;
   if (totals) std::memset(totals, 0, sizeof *totals);
   if (phases) std::memset(phases, 0, sizeof *phases);
   if (n_games == 0) return C4_OK;
-  if (net->channels != 32 && net->channels != 64) return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: the evaluator's kernels take 32 or 64 channels");
-  if (!net->w1 || !net->b1) return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: both heads need a hidden layer (the merged first layer w1 / b1)");
-  if (net->n_policy_hidden > 8 || net->n_value_hidden > 8) return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: at most 8 further hidden layers per head");
+  if (net->channels != 32 && net->channels != 64) return fail(C4_ERR_BAD_ARG, t_who + ": the evaluator's kernels take 32 or 64 channels");
+  if (!net->w1 || !net->b1) return fail(C4_ERR_BAD_ARG, t_who + ": both heads need a hidden layer (the merged first layer w1 / b1)");
+  if (net->n_policy_hidden > 8 || net->n_value_hidden > 8) return fail(C4_ERR_BAD_ARG, t_who + ": at most 8 further hidden layers per head");
   // One job at a time: a job captures HIP graphs, and a capture does not tolerate what another job's set-up does meanwhile (allocations,
   // memsets and transfers on the legacy stream: "operation would make the legacy stream depend on a capturing stream") -- two threads of
   // a host calling at once used to fail that way.  A job fills the device anyway; the second caller waits here.
-  static std::mutex one_job;
+  static std::mutex one_job;   // (one lock for both entry points)
   std::lock_guard<std::mutex> hold(one_job);
   g_cancel_requested.store(0, std::memory_order_relaxed);   // a request is for the job that was running when it was made
   const double t0 = now_s();
   c4host::DeviceGuard guard(opt.device);
-  if (guard.error() != hipSuccess) return fail(C4_ERR_HIP, std::string("c4_play_games_bf16: hipSetDevice: ") + hipGetErrorString(guard.error()));
+  if (guard.error() != hipSuccess) return fail(C4_ERR_HIP, t_who + ": hipSetDevice: " + hipGetErrorString(guard.error()));
 
   // ---- how many games are resident, in how many sessions, how many rounds per graph: c4a0_amd/api.py's rules (measured there)
   uint64_t resident = opt.resident_games;
@@ -221,7 +224,7 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
     resident = 4096;
     while (resident < 16384 && n_games >= 8 * resident) resident *= 2;
     const uint64_t n = std::max<uint32_t>(1u, n_mcts_iterations);
-    const uint64_t per_slot = 128ull * (n <= 1000 ? 43 * n + 8 : 2 * (5 * n / 2 + 554));
+    const uint64_t per_slot = 128ull * (search ? n + 8 : (n <= 1000 ? 43 * n + 8 : 2 * (5 * n / 2 + 554)));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
       while (resident > 4096 && resident * per_slot > free_b / 4) resident /= 2;
@@ -232,11 +235,12 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
   // (measured with the 32-channel network; the 64-channel one, five times the arithmetic per row, keeps the pair)
   const bool one_generation = n_games <= resident && net->channels <= 32;
   uint32_t n_parts = opt.concurrent_sessions ? opt.concurrent_sessions : ((resident >= 2048 && !one_generation) ? 2u : 1u);
-  if (n_parts > 2) return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: one session, or two paired ones");
+  if (n_parts > 2) return fail(C4_ERR_BAD_ARG, t_who + ": one session, or two paired ones");
   n_parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_parts, resident));
   const bool extensions = opt.dirichlet_epsilon > 0.0f || opt.eval_cache_entries != 0;
   const bool fused = !extensions;                       // what c4_session_step_head_out accepts (per-launch timing is switched off below)
-  const uint64_t est_rounds = ((n_games + resident - 1) / resident) * 15ull * std::max<uint32_t>(1u, n_mcts_iterations);
+  // rounds the job will take: ~15 moves x n simulations per generation of games; a search is n simulations, no moves
+  const uint64_t est_rounds = ((n_games + resident - 1) / resident) * (search ? 1ull : 15ull) * std::max<uint32_t>(1u, n_mcts_iterations);
   uint32_t steady = opt.steps_per_graph, tail = opt.tail_steps_per_graph;
   if (steady == 0) steady = n_parts == 2 ? (est_rounds >= 4000 ? 64u : (est_rounds >= 1500 ? 32u : 8u)) : (est_rounds >= 1500 ? 32u : 8u);
   if (tail == 0) tail = (n_parts == 1 && est_rounds >= 10000) ? steady : (steady >= 32 ? 16u : 8u);   // a long one-session job keeps its long graphs
@@ -256,13 +260,18 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
     cfg.c_exploration = c_exploration;
     cfg.c_ply_penalty = c_ply_penalty;
     cfg.planes_dtype = 1;
-    cfg.flags = opt.flags;
+    cfg.flags = opt.flags | (search ? C4_FLAG_SEARCH : 0u);
     cfg.device = opt.device;
     cfg.reclaim_period = opt.reclaim_period;
     C4_TRY(c4_session_create(&cfg, &part.s));
     std::vector<c4_game_metadata> mine(part.n_games);
     for (uint64_t i = 0; i < part.n_games; i++) mine[i] = reqs[i * n_parts + p];
-    C4_TRY(c4_session_set_games(part.s, mine.data(), part.n_games, nullptr, nullptr));
+    std::vector<uint64_t> mine_m, mine_v;
+    if (start_masks) {
+      mine_m.resize(part.n_games); mine_v.resize(part.n_games);
+      for (uint64_t i = 0; i < part.n_games; i++) { mine_m[i] = start_masks[i * n_parts + p]; mine_v[i] = start_values[i * n_parts + p]; }
+    }
+    C4_TRY(c4_session_set_games(part.s, mine.data(), part.n_games, start_masks ? mine_m.data() : nullptr, start_masks ? mine_v.data() : nullptr));
     if (opt.dirichlet_epsilon > 0.0f) C4_TRY(c4_session_set_dirichlet(part.s, opt.dirichlet_alpha, opt.dirichlet_epsilon));
     if (opt.eval_cache_entries) C4_TRY(c4_session_set_eval_cache(part.s, std::max<uint64_t>(1024, opt.eval_cache_entries / n_parts), 0));
 #ifdef C4_DIAG_VARIANTS   // diagnostic build only (build.py --diag): the chip PARTITIONED between the two sessions by CU masks (measured, not adopted)
@@ -341,7 +350,7 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
         c4_counters c{};
         (void)c4_session_counters(p.s, &c);
         if (totals) { totals->error = c.error; totals->error_slot = c.error_slot; }
-        return fail((int)(c.error ? c.error : err), "c4_play_games_bf16: raised on the device by slot " + std::to_string(c.error_slot));
+        return fail((int)(c.error ? c.error : err), t_who + ": raised on the device by slot " + std::to_string(c.error_slot));
       }
       done_all = done_all && p.done >= p.n_games;
       started_all = started_all && p.started >= p.n_games;
@@ -350,7 +359,7 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
     if (done_all) break;
     if (g_cancel_requested.load(std::memory_order_relaxed)) {
       (void)j.sync();
-      return fail(C4_ERR_CANCELLED, "c4_play_games_bf16: stopped by c4_play_games_cancel after " + std::to_string(steps) + " rounds");
+      return fail(C4_ERR_CANCELLED, t_who + ": stopped by c4_play_games_cancel after " + std::to_string(steps) + " rounds");
     }
     if (since_check >= 64 && started_all) {
       since_check = 0;
@@ -396,7 +405,7 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
     if (c.error && !sum.error) { sum.error = c.error; sum.error_slot = c.error_slot; }
   }
   if (totals) *totals = sum;
-  if (sum.error) return fail((int)sum.error, "c4_play_games_bf16: raised on the device by slot " + std::to_string(sum.error_slot));
+  if (sum.error) return fail((int)sum.error, t_who + ": raised on the device by slot " + std::to_string(sum.error_slot));
   MergeArgs margs{};
   margs.parts = n_parts;
   std::vector<uint32_t> part_counts;
@@ -412,8 +421,8 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
   for (uint64_t g = 0; g < n_games; g++) { offsets[g] = total; total += counts_host[g]; }
   *n_records = total;
   if (total > records_cap || (total && !records_host))
-    return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: " + std::to_string(total) + " records, room for " + std::to_string(records_cap) +
-                                " (43 per game always suffice)");
+    return fail(C4_ERR_BAD_ARG, t_who + ": " + std::to_string(total) + " records, room for " + std::to_string(records_cap) +
+                                (search ? "" : " (43 per game always suffice)"));
   if (total) {
     HIP_OK(hipMalloc(&j.offsets_dev, n_games * sizeof(unsigned long long)));
     HIP_OK(hipMalloc(&j.merged_dev, total * sizeof(c4_sample_rec)));
@@ -439,6 +448,48 @@ extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games
     phases->rows_at_end = 0;
     for (const Part& p : j.parts) phases->rows_at_end += p.rows;
   }
+  return C4_OK;
+}
+
+extern "C" int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games, uint32_t n_mcts_iterations, float c_exploration,
+                                  float c_ply_penalty, const c4_network_bf16* net, const c4_play_options* opt_in, uint32_t* counts_host,
+                                  c4_sample_rec* records_host, uint64_t records_cap, uint64_t* n_records, c4_counters* totals,
+                                  c4_play_phases* phases) {
+  t_who = "c4_play_games_bf16";
+  if (!net || !n_records || (n_games && (!reqs || !counts_host))) return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: null argument");
+  if (opt_in && (opt_in->flags & C4_FLAG_SEARCH)) return fail(C4_ERR_BAD_ARG, "c4_play_games_bf16: C4_FLAG_SEARCH is c4_search_positions_bf16's");
+  return run_job(reqs, nullptr, nullptr, false, n_games, n_mcts_iterations, c_exploration, c_ply_penalty, net, opt_in, counts_host, records_host,
+                 records_cap, n_records, totals, phases);
+}
+
+// ---- searches of given positions as ONE native call.  Replaces MctsGame::new_from_pos (mcts.rs:48-56) + the `run_mcts` helper of
+// mcts.rs' known-answer tests (mcts.rs:469-485: n x [leaf -> evaluator -> on_received_policy], then root_policy / root_q_*), which is
+// also what InteractivePlay::new_from_pos / snapshot (interactive_play.rs:33, 57) shows for ONE position -- for P positions at once:
+// position i is request (game_id = i, 0, 0) of a C4_FLAG_SEARCH job, played by the schedule above (paired sessions, HIP graphs, refill,
+// narrowing, merge in request order); its one record is records[i].
+extern "C" int c4_search_positions_bf16(const uint64_t* masks, const uint64_t* values, uint64_t n_positions, uint32_t n_mcts_iterations,
+                                        float c_exploration, float c_ply_penalty, const c4_network_bf16* net, const c4_play_options* opt_in,
+                                        c4_sample_rec* records, uint64_t records_cap, c4_counters* totals, c4_play_phases* phases) {
+  t_who = "c4_search_positions_bf16";
+  if (!net || (n_positions && (!masks || !values || !records))) return fail(C4_ERR_BAD_ARG, "c4_search_positions_bf16: null argument");
+  if (records_cap < n_positions)
+    return fail(C4_ERR_BAD_ARG, "c4_search_positions_bf16: " + std::to_string(n_positions) + " positions, room for " + std::to_string(records_cap) + " records (one per position)");
+  if (n_mcts_iterations == 0) return fail(C4_ERR_BAD_ARG, "c4_search_positions_bf16: n_mcts_iterations must be >= 1");
+  if (n_positions >= (1ull << 32) - 1) return fail(C4_ERR_BAD_ARG, "c4_search_positions_bf16: too many positions for one call");
+  if (opt_in) {
+    if (opt_in->dirichlet_epsilon > 0.0f) return fail(C4_ERR_BAD_ARG, "c4_search_positions_bf16: no Dirichlet noise in a search");
+    if (opt_in->eval_cache_entries) return fail(C4_ERR_BAD_ARG, "c4_search_positions_bf16: no evaluation cache in a search");
+    if (opt_in->flags & (C4_FLAG_RECLAIM | C4_FLAG_NO_RECLAIM | C4_FLAG_NO_MOVES))
+      return fail(C4_ERR_BAD_ARG, "c4_search_positions_bf16: a search never moves: its arena is never reclaimed (flags: C4_FLAG_ONE_SIM_PER_STEP only)");
+  }
+  std::vector<c4_game_metadata> reqs(n_positions);
+  for (uint64_t i = 0; i < n_positions; i++) reqs[i] = c4_game_metadata{i, 0, 0};
+  std::vector<uint32_t> counts(n_positions);
+  uint64_t n_records = 0;
+  const int rc = run_job(reqs.data(), masks, values, true, n_positions, n_mcts_iterations, c_exploration, c_ply_penalty, net, opt_in, counts.data(),
+                         records, records_cap, &n_records, totals, phases);
+  if (rc != C4_OK) return rc;
+  if (n_records != n_positions) return fail(C4_ERR_HIP, "c4_search_positions_bf16: " + std::to_string(n_records) + " records for " + std::to_string(n_positions) + " positions");
   return C4_OK;
 }
 

@@ -489,7 +489,11 @@ C4_DEV void timing_helper(const Params& p, uint32_t lane) {
 // `wave_index` = the wavefront's row in the per-wavefront arrays (games 8 wave_index .. + 7), `hot` = this lane's 16 bytes of its
 // game's state line, `nn_logit` / `nn_q` = the evaluator's outputs for the game (lane sub < 7: logit sub; q_penalty / q_no_penalty
 // on even / odd lanes), `t_start` = the wavefront's start stamp (timed launches).
-template <typename PlaneT, bool NOISE, bool CACHE>
+// SEARCH (C4_FLAG_SEARCH, an instantiation of its own like NOISE / CACHE: the default carries none of it): a game is ONE search of its
+// start position (mcts.rs:48-56 new_from_pos + the run_mcts helper, mcts.rs:469-485; interactive_play.rs:33, 57).  A terminal root is
+// searched like any other, the gate writes one record -- root policy and root q -- instead of moving, and the slot takes the next
+// request; no temperature, no move RNG.
+template <typename PlaneT, bool NOISE, bool CACHE, bool SEARCH = false>
 C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t lane, const uint32_t n_slots, Slot* st, const uint4 hot,
                       const float nn_logit, const float nn_q, const unsigned long long t_start, const uint32_t g) {
   // g = this lane group's game (>= n_slots: none).  The stand-alone kernels give a wavefront the 8 games 8 wave_index .. + 7; the fused
@@ -552,7 +556,8 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
       // makes it).  The reference gives such a root its n simulations, none of which can change the game's one sample
       // (self_play.rs:283-308, mcts.rs:271-313): as after a move into a terminal position, the game is closed now and the
       // simulations are counted as skipped.  (C4_FLAG_NO_MOVES, the reference's run_mcts, keeps searching such a root.)
-      const bool term_start = term != 0 && depth == 0 && !(p.flags & C4_FLAG_NO_MOVES);
+      // (A search keeps searching it too: its root q is q_sum / (n + 1), not the terminal value.)
+      const bool term_start = !SEARCH && term != 0 && depth == 0 && !(p.flags & C4_FLAG_NO_MOVES);
       // ---------------- on_received_policy: terminal value or expansion -------------------
       float v_pen, v_nopen;
       if (term) {
@@ -623,7 +628,8 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
       }
       root_n = shfl_u32(root_n, gbase + 4);
       c_sims += term_start ? 0u : 1u;
-      c_K += term_start ? 0u : depth + 1;
+      // (a search's simulations of a terminal root are not counted in K, as the oracle counts backup_nodes)
+      c_K += (term_start || (SEARCH && term != 0 && depth == 0)) ? 0u : depth + 1;
       // The stores above are read back below through other lanes of THIS wavefront.  A wavefront's
       // vector-memory instructions reach the cache in program order, so a later load of the same
       // address returns the stored bytes without waiting for the store's acknowledgement: only the
@@ -634,7 +640,32 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
 
       // ---------------- gate: self_play.rs:283-308 ------------------------------------------
       bool finished = false;
-      if ((root_n >= p.n_iter && !(p.flags & C4_FLAG_NO_MOVES)) || term_start) {
+      if (SEARCH && root_n >= p.n_iter) {
+        // The search is over: ONE record at the head of the request's 43, and the slot is free for the next request.
+        // root_policy (mcts.rs:396-412): child visit counts / their left-to-right sum; 1/7 each without children or visits
+        const uint4 re = load_block_lane(blocks, root_block, sub);          // (root_block == 0: the root's own block, not counted)
+        const float cnt = (sub < 7 && root_block != 0) ? (float)re.x : 0.0f;
+        float w[7];
+        float csum = 0.0f;
+        for (int i = 0; i < 7; i++) { w[i] = shfl_f32(cnt, gbase + i); csum = csum + w[i]; }
+        float pol[7];
+        for (int i = 0; i < 7; i++) pol[i] = (csum == 0.0f) ? (1.0f / 7.0f) : (w[i] / csum);
+        // root_q_with_penalty / root_q_no_penalty (mcts.rs:359-367): q_sum / (visit_count as f32 + 1.0), as c4_session_root_stats
+        const Entry* re0 = &blocks[root_ref >> 3].e[root_ref & 7];
+        const float nf = (float)re0->n + 1.0f;
+        const float rq_pen = re0->q_pen / nf, rq_nopen = re0->q_nopen / nf;
+        c4_sample_rec* rec = p.samples + (size_t)ordinal * C4_MAX_SAMPLES_PER_GAME;
+        if (sub < 7) rec->policy[sub] = pol[sub];
+        if (sub == 7) {
+          rec->game_id = game_id; rec->mask = rmask; rec->value = rvalue;
+          rec->q_penalty = rq_pen; rec->q_no_penalty = rq_nopen; rec->meta = 0u | (2u << 16);
+          p.sample_counts[ordinal] = 1;
+        }
+        c_done += 1;
+        c_samples += 1;
+        finished = true;
+      }
+      if (!SEARCH && ((root_n >= p.n_iter && !(p.flags & C4_FLAG_NO_MOVES)) || term_start)) {
         const size_t rec0 = (size_t)ordinal * C4_MAX_SAMPLES_PER_GAME;
         uint32_t rterm = term_start ? term : 0u;             // a root is terminal only as a terminal START position
         uint32_t retained = term_start ? 0u : p.n_iter;
@@ -724,7 +755,7 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
       }
       // Did any game of this wavefront move in this launch?  Asked here, where every game that entered the
       // trip is still in it (a wavefront's 8 games run in lock-step: one game's extra work is everybody's).
-      const bool wave_moved = __ballot(c_moves != 0) != 0ull;
+      const bool wave_moved = SEARCH ? false : (__ballot(c_moves != 0) != 0ull);   // (a search never moves)
       if (err) break;
 
       C4_STAMP_TRIP1(12, root_n);
@@ -826,7 +857,7 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
   // The launch lasts as long as its slowest wavefront, and that is one with a MOVING game.  The
   // ChaCha12 word a game will need at its next move depends only on (game_id, moves played), so it
   // is computed here, in a step where no game of this wavefront moved, and kept in the slot.
-  if (__ballot(c_moves != 0) == 0ull && pre_need) {
+  if (!SEARCH && __ballot(c_moves != 0) == 0ull && pre_need) {
     const uint32_t w = c4::rng_first_u32_group(pre_game_id * (uint64_t)(42 + pre_n_moves), sub, gbase);
     if (sub == 3) { line.w = w; line.x = (line.x & 0x03FFFFFFu) | ((pre_n_moves + 1u) << 26); }
   }
@@ -839,7 +870,7 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
   }
 }
 
-template <typename PlaneT, bool NOISE, bool CACHE>
+template <typename PlaneT, bool NOISE, bool CACHE, bool SEARCH = false>
 __global__ __launch_bounds__(64, (NOISE || CACHE) ? 1 : C4_STEP_WAVES) void c4_step_kernel(
     // What the head of every wavefront's dependent chain needs, as leading SCALAR arguments (copies of p's fields): with
     // -mllvm -amdgpu-kernarg-preload-count (build.py) they are in SGPRs when the wavefront starts, so the state line and
@@ -868,7 +899,7 @@ __global__ __launch_bounds__(64, (NOISE || CACHE) ? 1 : C4_STEP_WAVES) void c4_s
   // `if (active)` below, i.e. behind the wait for the state line -- a second, serial memory round trip (plus the
   // scalar loads of the two pointers) at the head of every wavefront's chain (round 3, found in the ISA).
   __builtin_amdgcn_sched_barrier(0);
-  step_body<PlaneT, NOISE, CACHE>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, t_start, g);
+  step_body<PlaneT, NOISE, CACHE, SEARCH>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, t_start, g);
 }
 
 // c4_session_scatter_outputs + c4_session_step as ONE launch (callback mode, c4_session_step_gather): a game takes its evaluator
@@ -923,7 +954,8 @@ __global__ __launch_bounds__(64, (NOISE || CACHE) ? 1 : C4_STEP_WAVES) void c4_s
 // (BASELINE config 2, the paired graph) 4 is +0.5 % (six of six alternating pairs), for a session alone (the reference's default job)
 // -0.4 %: the paired driver asks for 4, everybody else gets 8.  Which wavefront steps a game changes nothing the game records.
 // (Counter rows: two wavefronts add to one row, by atomics as before.)
-template <typename PlaneT, uint32_t kGpw>
+// SEARCH: the step of a search session (C4_FLAG_SEARCH, see step_body); the output layers are the same code.
+template <typename PlaneT, uint32_t kGpw, bool SEARCH = false>
 __global__ __launch_bounds__(64 * c4ho::kHeadWaves, 1) C4_OUT_STEP_ATTR void c4_out_step_kernel(
     const uint4* __restrict__ hp, const uint4* __restrict__ hv, const uint4* __restrict__ wp, const uint4* __restrict__ wv,
     const float* __restrict__ bp, const float* __restrict__ bv, Slot* __restrict__ a_slots, uint32_t a_n_slots, uint32_t f8, uint32_t sp8, uint32_t sv8,
@@ -946,7 +978,7 @@ __global__ __launch_bounds__(64 * c4ho::kHeadWaves, 1) C4_OUT_STEP_ATTR void c4_
   if (wave >= kStepWaves || wave_index >= p.n_waves) return;
   const float nn_logit = sh.res[b & 15][sub < 7 ? sub : 6];
   const float nn_q = sh.res[b & 15][7 + (sub & 1)];
-  step_body<PlaneT, false, false>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, 0ull, g);
+  step_body<PlaneT, false, false, SEARCH>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, 0ull, g);
   C4_TL_END(3, a_slots);
 }
 
@@ -1514,8 +1546,9 @@ static uint64_t reclaim_half_min(uint32_t n_iter, uint32_t period, uint32_t max_
 }
 static bool reclaim_mode(const c4_config* cfg) {
   return (cfg->flags & C4_FLAG_RECLAIM) != 0 ||
-         (cfg->blocks_per_slot == 0 && cfg->n_mcts_iterations > kReclaimAuto && !(cfg->flags & (C4_FLAG_NO_MOVES | C4_FLAG_NO_RECLAIM)));
+         (cfg->blocks_per_slot == 0 && cfg->n_mcts_iterations > kReclaimAuto && !(cfg->flags & (C4_FLAG_NO_MOVES | C4_FLAG_NO_RECLAIM | C4_FLAG_SEARCH)));
 }
+static bool search_mode(const c4_session* s) { return (s->cfg.flags & C4_FLAG_SEARCH) != 0; }
 
 // Called behind every step launch of a reclaimed session: every `period`-th launch is followed by k_arena_reclaim on the same
 // stream.  Launches are counted per capture while the stream is being captured into a HIP graph (the count restarts with the
@@ -1554,6 +1587,8 @@ static int session_create_on_device(const c4_config* cfg, c4_session* s) {
     s->p.half_blocks = (uint32_t)(bps / 2);
     bps = 2ull * s->p.half_blocks;
   } else {
+    // a search expands at most once per simulation and never re-roots: the root's own block + n, + slack
+    if (bps == 0 && (cfg->flags & C4_FLAG_SEARCH)) bps = (uint64_t)cfg->n_mcts_iterations + 8;
     if (bps == 0) bps = 43ull * (cfg->n_mcts_iterations ? cfg->n_mcts_iterations : 1) + 8;
     if (bps < 2) bps = 2;
   }
@@ -1621,6 +1656,13 @@ int c4_session_create(const c4_config* cfg, c4_session** out) {
   // reason; a caller who knows its games are short may still pass blocks_per_slot explicitly.
   // (From round 5 the default sizing switches to a RECLAIMED arena above 1 000 iterations, see C4_FLAG_RECLAIM: the live subtree is at
   // most n + a few blocks, so two halves of 2.5 n + 554 blocks (reclaim_half_min + 1.5 n of slack) serve any game and the links stay 16 bits wide up to n = 32 213.)
+  // A search session (C4_FLAG_SEARCH) never moves: nothing to reclaim, nothing C4_FLAG_NO_MOVES would add, and a gate at 0 visits
+  // would never be reached by a backup.
+  if (cfg->flags & C4_FLAG_SEARCH) {
+    if (cfg->flags & C4_FLAG_NO_MOVES) return fail(C4_ERR_BAD_ARG, "C4_FLAG_SEARCH and C4_FLAG_NO_MOVES exclude each other: a search ends at n_mcts_iterations visits and hands its slot on");
+    if (cfg->flags & C4_FLAG_RECLAIM) return fail(C4_ERR_BAD_ARG, "C4_FLAG_SEARCH: a search never moves, so its arena (n_mcts_iterations + 8 blocks) has nothing to reclaim (C4_FLAG_RECLAIM)");
+    if (cfg->n_mcts_iterations == 0) return fail(C4_ERR_BAD_ARG, "C4_FLAG_SEARCH needs n_mcts_iterations >= 1");
+  }
   if (reclaim_mode(cfg)) {
     const uint32_t period = cfg->reclaim_period ? cfg->reclaim_period : kReclaimPeriod;
     const uint64_t need = reclaim_half_min(cfg->n_mcts_iterations, period, 2);
@@ -1632,7 +1674,9 @@ int c4_session_create(const c4_config* cfg, c4_session** out) {
       return fail(C4_ERR_BAD_ARG, "reclaimed arena too small: each half must hold the live subtree (n_mcts_iterations + simulations per launch + 8 blocks) and the blocks of 4 x "
                                   "reclaim_period step launches (" + std::to_string(need) + " blocks per half, i.e. blocks_per_slot >= " + std::to_string(2 * need) +
                                   "; a half is at most 32 767 blocks: n_mcts_iterations <= " + std::to_string(kMaxBlocksPerSlot / 2 - (need - cfg->n_mcts_iterations)) + ")");
-  } else if (cfg->blocks_per_slot == 0 && 43ull * cfg->n_mcts_iterations + 8 > kMaxBlocksPerSlot)
+  } else if ((cfg->flags & C4_FLAG_SEARCH) && cfg->blocks_per_slot == 0 && (uint64_t)cfg->n_mcts_iterations + 8 > kMaxBlocksPerSlot)
+    return fail(C4_ERR_BAD_ARG, "C4_FLAG_SEARCH: n_mcts_iterations + 8 blocks per slot exceed 65535 (16-bit child links)");
+  else if (!(cfg->flags & C4_FLAG_SEARCH) && cfg->blocks_per_slot == 0 && 43ull * cfg->n_mcts_iterations + 8 > kMaxBlocksPerSlot)
     return fail(C4_ERR_BAD_ARG, "n_mcts_iterations > 1523 is not supported with a never-reclaimed arena (C4_FLAG_NO_MOVES / C4_FLAG_NO_RECLAIM): a game's tree arena is limited to "
                                 "65535 blocks (16-bit child links; up to 43 n + 8 blocks per game). "
                                 "Pass blocks_per_slot explicitly to accept C4_ERR_ARENA_OVERFLOW on long searches");
@@ -1766,6 +1810,7 @@ int c4_session_bind_io(c4_session* s, void* planes_dev, const float* logprobs_de
 int c4_session_set_dirichlet(c4_session* s, float alpha, float epsilon) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (!(epsilon >= 0.0f && epsilon <= 1.0f) || (epsilon > 0.0f && !(alpha > 0.0f))) return fail(C4_ERR_BAD_ARG, "need 0 <= epsilon <= 1 and alpha > 0");
+  if (epsilon > 0.0f && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_dirichlet: a search session (C4_FLAG_SEARCH) has no Dirichlet-noise step kernel");
   s->p.dir_alpha = alpha;
   s->p.dir_eps = epsilon;
   return C4_OK;
@@ -1773,6 +1818,7 @@ int c4_session_set_dirichlet(c4_session* s, float alpha, float epsilon) {
 
 int c4_session_bind_leaf_models(c4_session* s, uint64_t* leaf_models_dev) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
+  if (leaf_models_dev && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_bind_leaf_models: a search session (C4_FLAG_SEARCH) has ONE evaluator");
   if (leaf_models_dev && s->p.cache) return fail(C4_ERR_BAD_ARG, "the evaluation cache holds ONE evaluator's outputs: not with multi-model games");
   s->p.leaf_models = leaf_models_dev;
   return C4_OK;
@@ -1782,6 +1828,7 @@ int c4_session_set_eval_cache(c4_session* s, uint64_t n_entries, uint32_t max_si
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (n_entries && s->p.leaf_models) return fail(C4_ERR_BAD_ARG, "the evaluation cache holds ONE evaluator's outputs: not with multi-model games");
   if (n_entries > (1ull << 31)) return fail(C4_ERR_BAD_ARG, "at most 2^31 cache entries");
+  if (n_entries && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_eval_cache: a search session (C4_FLAG_SEARCH) has no evaluation-cache step kernel");
   C4_ON_DEVICE(s->cfg.device);
   HIP_TRY(hipStreamSynchronize(s->stream));
   (void)hipFree(s->p.cache);
@@ -1857,7 +1904,9 @@ static int launch_step(c4_session* s, const uint32_t* inverse, const float* answ
       else       { if (cache) LAUNCH(KERNEL<uint16_t, false, true>); else LAUNCH(KERNEL<uint16_t, false, false>); }  \
     }                                                                                                                \
   } while (0)
-  if (inverse) C4_LAUNCH_STEP(c4_step_gather_kernel, launch_gather); else C4_LAUNCH_STEP(c4_step_kernel, launch);
+  if (search_mode(s)) {   // no noise, cache or gather form (refused where they are asked for)
+    if (f32) launch(c4_step_kernel<float, false, false, true>); else launch(c4_step_kernel<uint16_t, false, false, true>);
+  } else if (inverse) C4_LAUNCH_STEP(c4_step_gather_kernel, launch_gather); else C4_LAUNCH_STEP(c4_step_kernel, launch);
 #undef C4_LAUNCH_STEP
   HIP_TRY(hipGetLastError());
   return maybe_reclaim(s);
@@ -1867,6 +1916,7 @@ int c4_session_step(c4_session* s) { return launch_step(s, nullptr, nullptr, 0);
 
 int c4_session_step_gather(c4_session* s, const uint32_t* inverse_dev, const float* answers, uint32_t n_unique) {
   if (!s || !inverse_dev || (!answers && n_unique)) return fail(C4_ERR_BAD_ARG, "null argument");
+  if (search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_step_gather: a search session (C4_FLAG_SEARCH) takes a device evaluator, not the callback mode's batches");
   if (!s->bound) return fail(C4_ERR_NOT_BOUND, "c4_session_step_gather: bind_io first");
   void *inv = nullptr, *ans = nullptr;
   {
@@ -1897,7 +1947,11 @@ int c4_session_step_head_out(c4_session* s, const void* hidden_policy_dev, const
                        (const uint4*)w_policy_dev, (const uint4*)w_value_dev, b_policy_dev, b_value_dev, s->p.slots, s->p.n_slots, features / 8,
                        policy_row_stride / 8, value_row_stride / 8, s->p);
   };
-  if (s->out_step_gpw == 4) {
+  if (search_mode(s)) {
+    if (s->cfg.planes_dtype == 0)
+      return fail(C4_ERR_BAD_ARG, "c4_session_step_head_out: a search session's fused launch is built for bf16 planes (planes_dtype 1): call c4_head_out_bf16 and c4_session_step");
+    if (s->out_step_gpw == 4) launch(c4_out_step_kernel<uint16_t, 4, true>); else launch(c4_out_step_kernel<uint16_t, 8, true>);
+  } else if (s->out_step_gpw == 4) {
     if (s->cfg.planes_dtype == 0) launch(c4_out_step_kernel<float, 4>); else launch(c4_out_step_kernel<uint16_t, 4>);
   } else {
     if (s->cfg.planes_dtype == 0) launch(c4_out_step_kernel<float, 8>); else launch(c4_out_step_kernel<uint16_t, 8>);
@@ -2169,6 +2223,7 @@ static int device_view(const void* ptr, int device, const char* what, void** out
 
 int c4_session_unique_leaves(c4_session* s, uint32_t* inverse_dev, float* rows_out, uint64_t* models_out, uint32_t* n_unique_out) {
   if (!s || !inverse_dev || !rows_out || !n_unique_out) return fail(C4_ERR_BAD_ARG, "null argument");
+  if (search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: a search session (C4_FLAG_SEARCH) takes a device evaluator, not the callback mode's batches");
   if (!s->bound || !s->have_games) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: bind_io and set_games first");
   C4_ON_DEVICE(s->cfg.device);
   const uint32_t n = s->cfg.n_slots;

@@ -73,8 +73,11 @@ def _call_interruptibly(call):
 
 def run_native(ids: np.ndarray, n_mcts_iterations: int, c_exploration: float, c_ply_penalty: float, net, *, resident_games=None,
                concurrent_sessions=None, steps_per_graph: int = 0, tail_steps_per_graph: int = 0, blocks_per_slot: int = 0, reclaim=None,
-               reclaim_period: int = 0, dirichlet=None, eval_cache_entries: int = 0, stats: Optional[dict] = None, on_device: bool = False):
-    """One `c4_play_games_bf16` call for the requests `ids` (uint64[n, 3]): (records, counts) in request order; `stats` receives the
+               reclaim_period: int = 0, dirichlet=None, eval_cache_entries: int = 0, stats: Optional[dict] = None, on_device: bool = False,
+               start_positions: Optional[np.ndarray] = None, search: bool = False):
+    """search=True: one `c4_search_positions_bf16` call for the positions `start_positions` (uint64[n, 2]; `ids` must be (i, 0, 0)):
+    one record per position, counts all 1.  Otherwise:
+    One `c4_play_games_bf16` call for the requests `ids` (uint64[n, 3]): (records, counts) in request order; `stats` receives the
     sessions' counters and where the call's wall time went, under the keys the Python loop uses (c4a0_amd/api.py _play).
     on_device=True: the records stay on the GPU, a uint8[n, 64] tensor (what the multi-GPU path all-gathers)."""
     import torch
@@ -92,8 +95,10 @@ def run_native(ids: np.ndarray, n_mcts_iterations: int, c_exploration: float, c_
     if dirichlet is not None:
         opt.dirichlet_alpha, opt.dirichlet_epsilon = float(dirichlet[0]), float(dirichlet[1])
     opt.eval_cache_entries = int(eval_cache_entries)
-    counts = np.empty(n, dtype=np.uint32)
-    cap = n * _lib.MAX_SAMPLES_PER_GAME                                      # 43 per game always suffice
+    if (start_positions is not None) != bool(search):
+        raise ValueError("the library's loop plays whole games from the empty board, or searches given positions")
+    counts = np.ones(n, dtype=np.uint32) if search else np.empty(n, dtype=np.uint32)
+    cap = n if search else n * _lib.MAX_SAMPLES_PER_GAME                     # 43 per game always suffice
     if on_device:
         recs = torch.empty((cap, 64), dtype=torch.uint8, device=net.device)
         recs_ptr = recs.data_ptr()
@@ -102,9 +107,17 @@ def run_native(ids: np.ndarray, n_mcts_iterations: int, c_exploration: float, c_
         recs_ptr = recs.ctypes.data
     n_recs, totals, phases = C.c_uint64(), _lib.Counters(), _lib.PlayPhases()
     tab = np.ascontiguousarray(ids, dtype=np.uint64)
-    _call_interruptibly(lambda: _lib.check(_lib.lib().c4_play_games_bf16(
-        tab.ctypes.data, n, int(n_mcts_iterations), float(c_exploration), float(c_ply_penalty), C.byref(ns), C.byref(opt), counts.ctypes.data, recs_ptr, cap,
-        C.byref(n_recs), C.byref(totals), C.byref(phases))))
+    if search:
+        pos = np.ascontiguousarray(start_positions, dtype=np.uint64).reshape(n, 2)
+        masks, values = np.ascontiguousarray(pos[:, 0]), np.ascontiguousarray(pos[:, 1])
+        _call_interruptibly(lambda: _lib.check(_lib.lib().c4_search_positions_bf16(
+            masks.ctypes.data, values.ctypes.data, n, int(n_mcts_iterations), float(c_exploration), float(c_ply_penalty), C.byref(ns), C.byref(opt), recs_ptr, cap,
+            C.byref(totals), C.byref(phases))))
+        n_recs.value = n
+    else:
+        _call_interruptibly(lambda: _lib.check(_lib.lib().c4_play_games_bf16(
+            tab.ctypes.data, n, int(n_mcts_iterations), float(c_exploration), float(c_ply_penalty), C.byref(ns), C.byref(opt), counts.ctypes.data, recs_ptr, cap,
+            C.byref(n_recs), C.byref(totals), C.byref(phases))))
     if stats is not None:
         ph = phases.as_dict()
         stats.update(totals.as_dict())

@@ -533,3 +533,53 @@ def results_from_records(reqs, recs: np.ndarray, counts: np.ndarray) -> PlayGame
     reqs order) and the per-game sample counts; `GameResult`/`Sample` objects are created lazily.
     `reqs`: GameMetadata-like objects, or a uint64[n, 3] array of (game_id, player0_id, player1_id)."""
     return PlayGamesResult._from_records(reqs, recs, counts)
+
+
+# the packed 64-byte record of include/c4a0_hip.h c4_sample_rec (== c4a0_amd.session.SAMPLE_DTYPE, restated here so that a result
+# can be built and read without loading torch)
+RECORD_DTYPE = np.dtype([("game_id", "<u8"), ("mask", "<u8"), ("value", "<u8"), ("policy", "<f4", (7,)),
+                         ("q_penalty", "<f4"), ("q_no_penalty", "<f4"), ("meta", "<u4")])
+SEARCH_RECORD_META = 2 << 16   # c4_sample_rec.meta of a search record: index 0, flag bit 1
+
+
+class SearchResult:
+    """What `search_positions` returns: for each of the P positions, in the order given, the root policy and the two root q values
+    after the search (MctsGame::root_policy / root_q_with_penalty / root_q_no_penalty, mcts.rs:248-268), as columns of the packed
+    records the GPU handed over -- no Python object per position until `samples()` is asked for.
+
+    mask, value: uint64[P];  policy: float32[P, 7];  q_penalty, q_no_penalty: float32[P];  records: the structured array itself."""
+
+    DTYPE = RECORD_DTYPE
+    __slots__ = ("records",)
+
+    def __init__(self, records: np.ndarray):
+        recs = np.asarray(records)
+        if recs.dtype != RECORD_DTYPE:
+            if recs.dtype == np.uint8 and recs.ndim == 2 and recs.shape[1] == RECORD_DTYPE.itemsize:   # the on_device form, copied to the host
+                recs = np.ascontiguousarray(recs).reshape(-1).view(RECORD_DTYPE)
+            else:
+                raise TypeError("SearchResult takes the packed 64-byte records (c4a0_amd.session.SAMPLE_DTYPE, or uint8[P, 64])")
+        self.records = recs.reshape(-1)
+
+    mask = property(lambda self: self.records["mask"])
+    value = property(lambda self: self.records["value"])
+    policy = property(lambda self: self.records["policy"])
+    q_penalty = property(lambda self: self.records["q_penalty"])
+    q_no_penalty = property(lambda self: self.records["q_no_penalty"])
+
+    def best_moves(self) -> np.ndarray:
+        """int64[P]: the column of each policy's maximum, the FIRST one among equals, as Solution::score_policy picks it."""
+        return np.argmax(self.records["policy"], axis=1).astype(np.int64) if len(self.records) else np.zeros(0, dtype=np.int64)
+
+    def samples(self) -> List[Sample]:
+        """One Sample (types.rs:103-110) per position: (pos, root policy, root q_penalty, root q_no_penalty)."""
+        return Sample._bulk(self.records)
+
+    def __len__(self) -> int:
+        return len(self.records)
+
+    def __eq__(self, o):
+        return isinstance(o, SearchResult) and self.records.tobytes() == o.records.tobytes()
+
+    def __repr__(self):
+        return f"SearchResult({len(self.records)} positions)"

@@ -59,8 +59,12 @@ class DeviceSession:
     def __init__(self, n_slots: int, n_mcts_iterations: int, c_exploration: float, c_ply_penalty: float,
                  device: Optional[torch.device] = None, planes_dtype: torch.dtype = torch.float32,
                  blocks_per_slot: int = 0, no_moves: bool = False, one_sim_per_step: bool = False,
-                 reclaim: Optional[bool] = None, reclaim_period: int = 0):
-        """reclaim: True = the tree arena is reclaimed while games are played (C4_FLAG_RECLAIM: the live subtree is copied into the
+                 reclaim: Optional[bool] = None, reclaim_period: int = 0, search: bool = False):
+        """search: True = every request is ONE search of its start position (set_games(reqs, start_positions)), not a game:
+        n_mcts_iterations simulations, then one record -- the root policy and the root's two q values, meta = 2 << 16 -- and the slot
+        takes the next request (C4_FLAG_SEARCH; MctsGame::new_from_pos + run_mcts, mcts.rs:48-56, 469-485).  Device evaluators only;
+        no Dirichlet noise, evaluation cache or reclaimed arena.  compact / capture_steps / run / run_sessions / capture_pair as for games.
+        reclaim: True = the tree arena is reclaimed while games are played (C4_FLAG_RECLAIM: the live subtree is copied into the
         arena's other half when one runs short, as the reference frees dead subtrees at every move, mcts.rs:187-206); None = the
         library decides (on above 1 000 iterations per move with the default sizing); False with more than 1 523 iterations needs
         an explicit blocks_per_slot.  reclaim_period: step launches between two looks at the arenas (0 = 64; tests use 1)."""
@@ -78,7 +82,9 @@ class DeviceSession:
         cfg = Config(self.n_slots, int(blocks_per_slot), self.n_mcts_iterations, float(c_exploration),
                      float(c_ply_penalty), 0 if planes_dtype == torch.float32 else 1,
                      (_lib.FLAG_NO_MOVES if no_moves else 0) | (_lib.FLAG_ONE_SIM_PER_STEP if one_sim_per_step else 0) |
-                     (_lib.FLAG_RECLAIM if reclaim else (_lib.FLAG_NO_RECLAIM if reclaim is False else 0)), dev_index, int(reclaim_period))
+                     (_lib.FLAG_RECLAIM if reclaim else (_lib.FLAG_NO_RECLAIM if reclaim is False else 0)) |
+                     (_lib.FLAG_SEARCH if search else 0), dev_index, int(reclaim_period))
+        self.search = bool(search)
         h = C.c_void_p()
         check(self.L.c4_session_create(C.byref(cfg), C.byref(h)))
         self._h = h
@@ -116,8 +122,13 @@ class DeviceSession:
         if start_positions is not None:
             if len(start_positions) != n:
                 raise ValueError("start_positions must match reqs")
-            sm = (C.c_uint64 * max(1, n))(*[int(m) for m, _ in start_positions])
-            sv = (C.c_uint64 * max(1, n))(*[int(v) for _, v in start_positions])
+            if isinstance(start_positions, np.ndarray):   # uint64[n, 2]: no per-position Python work
+                cols = np.ascontiguousarray(start_positions, dtype=np.uint64).reshape(-1, 2)
+                keep = (np.ascontiguousarray(cols[:, 0]), np.ascontiguousarray(cols[:, 1]))   # (alive across the call below)
+                sm, sv = (C.cast(a.ctypes.data, C.POINTER(C.c_uint64)) if n else None for a in keep)
+            else:
+                sm = (C.c_uint64 * max(1, n))(*[int(m) for m, _ in start_positions])
+                sv = (C.c_uint64 * max(1, n))(*[int(v) for _, v in start_positions])
         check(self.L.c4_session_set_games(self._h, arr, n, sm, sv))   # copies the list (c4a0_hip.h): `tab` may go
         self.n_games = n
         self.rows = self.n_slots
@@ -143,8 +154,9 @@ class DeviceSession:
 
     def bind_leaf_models(self) -> torch.Tensor:
         """int64[n_slots] tensor that start()/step() fill with the model id to evaluate each leaf with."""
-        self.leaf_models = torch.zeros(self.n_slots, dtype=torch.int64, device=self.device)
-        check(self.L.c4_session_bind_leaf_models(self._h, C.c_void_p(self.leaf_models.data_ptr())))
+        models = torch.zeros(self.n_slots, dtype=torch.int64, device=self.device)
+        check(self.L.c4_session_bind_leaf_models(self._h, C.c_void_p(models.data_ptr())))   # (refused on a search session)
+        self.leaf_models = models
         return self.leaf_models
 
     def arena(self) -> dict:
@@ -176,7 +188,7 @@ class DeviceSession:
         capture), the heads' output layers run inside the step's launch (c4_session_step_head_out: one launch fewer on the
         round's chain, same bits); otherwise evaluate() then step()."""
         if (self.fuse_output_step and not self._timing and not self._extensions and getattr(self, "leaf_models", None) is None
-                and getattr(evaluator, "fused_step_ok", False)):
+                and getattr(evaluator, "fused_step_ok", False) and not (self.search and self.planes.dtype != torch.bfloat16)):   # (a search's fused launch: bf16 planes)
             r = self.rows
             p, v = evaluator.forward_hidden(self.planes if r == self.n_slots else self.planes[:r])
             wp, wv, bp, bv = evaluator.head_out_operands()

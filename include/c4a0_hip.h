@@ -24,10 +24,10 @@ extern "C" {
 #endif
 
 /* Version of THIS interface: bumped whenever a signature or a struct layout below changes (version 3 added `config` in the
- * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED, version 11 the f32 evaluator c4_conv_tower_f32 / c4_linear_f32 / c4_head_out_f32).  A consumer compiled against this header checks it once at start-up --
+ * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED, version 11 the f32 evaluator c4_conv_tower_f32 / c4_linear_f32 / c4_head_out_f32, version 12 C4_FLAG_SEARCH / c4_search_positions_bf16).  A consumer compiled against this header checks it once at start-up --
  * `if (c4_abi_version() != C4_ABI_VERSION) refuse` -- because the dynamic linker compares names, not signatures
  * (tests/abi_consumer*.c and c4a0_amd/_lib.py do).  No reference counterpart: the reference's boundary is PyO3. */
-#define C4_ABI_VERSION 11
+#define C4_ABI_VERSION 12
 
 #define C4_N_COLS 7          /* rust/src/c4r.rs:45, lib.rs:28 */
 #define C4_N_ROWS 6          /* rust/src/c4r.rs:44, lib.rs:29 */
@@ -57,7 +57,9 @@ typedef struct {
 } c4_game_metadata;
 
 /* One training sample (types.rs:103-110 Sample + the game it belongs to), 64 bytes.
- * meta = sample index within the game (low 16 bits) | flags << 16 (bit 0: terminal sample). */
+ * meta = sample index within the game (low 16 bits) | flags << 16 (bit 0: terminal sample; bit 1: search record -- the one
+ * record of a C4_FLAG_SEARCH request: policy = the root policy after n_mcts_iterations simulations, q_penalty / q_no_penalty = the
+ * root's q values, mcts.rs:359-367, 396-412 -- not a training sample of a game). */
 typedef struct {
   uint64_t game_id;
   uint64_t mask;   /* c4r.rs:13-17 Pos.mask  */
@@ -74,7 +76,8 @@ typedef struct {
   uint32_t blocks_per_slot;   /* tree arena per slot, in 128-byte 7-children blocks, at most 65535 (16-bit child links).
                                  0 = automatic: up to n_mcts_iterations = 1000 the worst case of a never-reclaimed arena,
                                  43*n_mcts_iterations+8; beyond that (and up to 32 200) a RECLAIMED arena of two halves of
-                                 2.5*n_mcts_iterations+554 blocks each (see C4_FLAG_RECLAIM) */
+                                 2.5*n_mcts_iterations+554 blocks each (see C4_FLAG_RECLAIM); a search session (C4_FLAG_SEARCH):
+                                 n_mcts_iterations+8 */
   uint32_t n_mcts_iterations; /* self_play.rs:43 */
   float c_exploration;        /* self_play.rs:44 (f32, as pybridge.rs:26) */
   float c_ply_penalty;        /* self_play.rs:45 */
@@ -100,6 +103,22 @@ typedef struct {
 
 #define C4_FLAG_NO_RECLAIM 8u /* keep the never-reclaimed arena where the default sizing would reclaim (n_mcts_iterations > 1000): 43 n + 8
                                  blocks per slot, refused beyond n = 1523 with the reason */
+
+#define C4_FLAG_SEARCH 16u    /* every request is ONE search, not a game: n_mcts_iterations simulations from its start position as root
+                                 (MctsGame::new_from_pos, mcts.rs:48-56, + the run_mcts helper of its tests, mcts.rs:469-485; what
+                                 interactive_play.rs:33, 57 shows), then ONE record at the head of the request's 43 -- mask / value = the
+                                 position, policy = root_policy (mcts.rs:396-412), q_penalty / q_no_penalty = q_sum / (visits + 1)
+                                 (mcts.rs:359-367), meta = 2 << 16 -- sample count 1, and the slot takes the next request.  No move, no
+                                 temperature, no move RNG.  A terminal position is searched n times like any other (its q is
+                                 q_sum / (n + 1), not the terminal value), two simulations per launch.  Counters of a finished job of P
+                                 positions: sims = P n, games_done = samples = games_started = P, moves = ref_skipped_sims = 0;
+                                 select_levels leaves out the select behind each search's last simulation (nobody consumes its leaf),
+                                 backup_nodes the simulations of a terminal root.  Automatic arena: n_mcts_iterations + 8 blocks per slot
+                                 (one expansion per simulation at most, never a re-root), so the 1 523-iteration limit of whole games
+                                 does not apply.  A step-kernel instantiation of its own: refused together with C4_FLAG_NO_MOVES,
+                                 C4_FLAG_RECLAIM or n_mcts_iterations == 0, and c4_session_set_dirichlet (epsilon > 0),
+                                 c4_session_set_eval_cache (n > 0), c4_session_bind_leaf_models, c4_session_step_gather and
+                                 c4_session_unique_leaves return C4_ERR_BAD_ARG on such a session. */
 
 /* Device-side counters (the reference's progress bars, self_play.rs:352-381, plus the
  * roofline numerators of SURVEY 8d).  Sums over all games since set_games. */
@@ -330,7 +349,18 @@ int c4_play_games_bf16(const c4_game_metadata* reqs, uint64_t n_games, uint32_t 
                        float c_ply_penalty, const c4_network_bf16* net, const c4_play_options* options, uint32_t* counts_host,
                        c4_sample_rec* records_host, uint64_t records_cap, uint64_t* n_records, c4_counters* totals,
                        c4_play_phases* phases);
-/* Asks the c4_play_games_bf16 call that is running (on whatever thread) to stop: it returns C4_ERR_CANCELLED after the graph replays
+/* Searches of given positions (ABI 12): MctsGame::new_from_pos (mcts.rs:48-56) + n_mcts_iterations x [leaf -> evaluator ->
+ * on_received_policy] (the run_mcts helper, mcts.rs:469-485; InteractivePlay::new_from_pos / snapshot, interactive_play.rs:33, 57) for
+ * EVERY position (masks[i], values[i]) -- any position, terminal ones included -- as one job of C4_FLAG_SEARCH sessions on
+ * c4_play_games_bf16's schedule.  records[i] = position i's record (game_id = i, mask / value = the position, policy = the root policy,
+ * q_penalty / q_no_penalty = the root's q, meta = 2 << 16), exactly n_positions of them, in host memory or DEVICE memory of
+ * options->device.  records_cap < n_positions, n_mcts_iterations == 0, and options with Dirichlet noise, an evaluation cache or a
+ * reclaim flag -> C4_ERR_BAD_ARG.  totals / phases may be NULL.  Synchronous; shares c4_play_games_bf16's one-job lock and
+ * c4_play_games_cancel.  The positions are not validated (c4a0_amd.api.search_positions does that on the host). */
+int c4_search_positions_bf16(const uint64_t* masks, const uint64_t* values, uint64_t n_positions, uint32_t n_mcts_iterations,
+                             float c_exploration, float c_ply_penalty, const c4_network_bf16* net, const c4_play_options* options,
+                             c4_sample_rec* records, uint64_t records_cap, c4_counters* totals, c4_play_phases* phases);
+/* Asks the c4_play_games_bf16 / c4_search_positions_bf16 call that is running (on whatever thread) to stop: it returns C4_ERR_CANCELLED after the graph replays
  * in flight (milliseconds), with everything given back and no records.  For a host's interrupt handling -- the reference's job is
  * stopped by killing the process; a job here can be minutes of one library call.  Has no effect when no job is running (a job
  * clears the request when it starts), and none on the c4_session_* entry points.  Callable from any thread. */
