@@ -543,7 +543,17 @@ int c4_head_out_bf16(const void* hidden_policy_dev, const void* hidden_value_dev
  *   linear     X = the layer's input row; act = relu(s) = (s > 0 ? s : 0) for hidden layers
  *   head out   policy v[0..6] = s, value v[7..8] = s (no activation), then logp[o] = v[o] - lse with mx = fmaxf over v[0..6] left to
  *              right, sum = ((0 + e0) + e1) + .. + e6, e_o = c4_expf(v[o] - mx) (glibc expf), lse = mx + c4_logf(sum) (glibc logf);
- *              q[i] = tanhf(v[7 + i]) (device libm) */
+ *              q[i] = tanhf(v[7 + i]) (device libm)
+ *
+ * Non-finite values follow from these rules by IEEE 754 arithmetic (no input is rejected or clamped; a NaN's payload is not specified):
+ *   chain      a NaN input or weight makes every sum it enters NaN, and so does Inf x 0 (a zero weight, a zero-padded input); Inf
+ *              otherwise gives +-Inf, or NaN where both signs meet.  Only the sums an element enters are affected: in the tower the cells
+ *              within the receptive field of a non-finite plane value, on its board; no other cell, board or row.
+ *   linear     without ReLU a NaN sum comes through; relu(s) = (s > 0 ? s : 0) turns NaN and -Inf into +0.0 and keeps +Inf.
+ *   head out   a NaN logit gives seven NaN log-probabilities (fmaxf skips it, so mx is the largest other logit, but its expf is NaN
+ *              and so are the sum and lse); a +Inf logit gives seven NaN (Inf - Inf); -Inf logits give -Inf there and leave the others
+ *              what they are without them (their expf is +0), unless all seven are -Inf (seven NaN).  q = tanhf: +-Inf give +-1.0
+ *              exactly, NaN gives NaN. */
 
 /* The tower (nn.py:64-70, 184-195): planes_dev f32 [n_boards][2][6][7] -> out_dev f32 [n_boards][42][channels] (cell-major, the padded
  * channels are 0).  channels = Cp (16, 32, 48 or 64); w0_dev [Cp][32], w_dev [2 n_blocks][Cp][9 Cp], bias_dev [1 + 2 n_blocks][Cp];

@@ -23,7 +23,9 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 import f32_ref as R  # noqa: E402
 
 TOL = 1e-5
-MATRIX = [(0, 16, 1, 1), (1, 32, 4, 2), (4, 32, 4, 2), (1, 37, 2, 2), (1, 64, 4, 2)]
+# the last two: heads of unequal depth, so no merged first layer and output layers of different widths -- (2, 3, 1, 3): the policy
+# output reads the 672 features, the value output its 128-wide hidden layer; (1, 20, 3, 1): policy 864 (hidden), value 1 344 (features)
+MATRIX = [(0, 16, 1, 1), (1, 32, 4, 2), (4, 32, 4, 2), (1, 37, 2, 2), (1, 64, 4, 2), (2, 3, 1, 3), (1, 20, 3, 1)]
 
 
 def random_model(cfg, seed):
