@@ -218,6 +218,30 @@ int c4_session_start(c4_session* s);
  * finished games, select the next leaves and write them to planes_dev.  Asynchronous. */
 int c4_session_step(c4_session* s);
 
+/* Non-finite evaluator outputs, sessions of games and of searches alike (every step entry point: c4_session_step, _step_gather,
+ * _step_head_out, with noise, cache, reclaimed arenas, HIP graphs).  No answer is rejected or clamped; a game ends as the reference
+ * would panic, game by game: the slot's status byte (c4_session_leaves) becomes the code and stays, the slot is never refilled, the
+ * game has no record, the first code raised is in c4_counters.error / error_slot, and every other game -- the seven of the same
+ * wavefront included -- goes on and records the reference's bytes.  Pinned against the oracle by tests/test_gpu_nonfinite_regime.py
+ * (games, every launch form) and tests/test_gpu_search_positions.py T5 (searches); the kinds are tests/helpers.py POISON_KINDS.
+ *   NaN q_penalty        backed up along the path; C4_ERR_NAN_IN_TREE at the next select that compares it with another candidate
+ *                        (utils.rs:12).  Down a chain of nodes with ONE legal column nothing is compared: no error, and a search
+ *                        record's root q is NaN (a game's records hold terminal values only).
+ *   NaN q_no_penalty     never compared: no error; a search record carries it.  A NaN's sign and payload are not specified.
+ *   +Inf q_penalty       scores of +-Inf compare like any other; C4_ERR_NAN_IN_TREE once +Inf and -Inf have met in one q_sum.
+ *   NaN legal logit      f32::max ignores it, its expf is NaN and so is every prior of the node: C4_ERR_NAN_IN_TREE when a select
+ *                        reaches the node, if it has two or more children.  On the ONLY legal column the masked maximum is -Inf:
+ *                        C4_ERR_DEGENERATE_POLICY at the expansion (mcts.rs:421-425).
+ *   NaN / any value on a full column   masked before the softmax (c4r.rs:272-286): no effect.
+ *   -Inf on some legal logits          priors of exactly 0.
+ *   -Inf on all legal logits, +Inf on a legal one   C4_ERR_DEGENERATE_POLICY at the expansion; nothing is backed up.
+ * One counted deviation: the reference selects a leaf BEHIND the simulation that completes a root's n visits
+ * and throws it away (the move selects again from the new root; a search's caller reads the root).  The device leaves that select
+ * out.  A NaN which that select alone would have compared therefore ends the game in the reference and not here: the game moves
+ * on, and ends with C4_ERR_NAN_IN_TREE later if the NaN sits in the subtree the move keeps, or finishes (a search: writes its
+ * record, root q possibly NaN).  The oracle plays either order (c4o_game_set_device_order); tests/test_nonfinite_regime.py pins
+ * on the CPU which games differ: 6 of 800 at n = 8 with one position in 300 poisoned, none of 600 at n = 24. */
+
 /* c4_head_out_bf16 (below) + c4_session_step as ONE launch: the heads' output layers (nn.py:84-85, 98-99) are computed by
  * workgroups of 16 boards whose first two wavefronts go on as the step of those 16 games (mcts.rs:83-108, self_play.rs:268-323):
  * one launch boundary and the step's argument fetch / state-line round trip leave the per-round chain.  The outputs are also

@@ -351,10 +351,16 @@ static inline float rust_f32_max(float a, float b) {
   return a > b ? a : b;
 }
 
+/* the maximum a NaN-propagating fold would give (C4O_TWIN_NAN_MAX: a mutant of the rule above, see c4o_game_set_twin) */
+static inline float nan_propagating_max(float a, float b) {
+  if (a != a || b != b) return NAN;
+  return a > b ? a : b;
+}
+
 /* mcts.rs:416-434 */
-int c4o_softmax7(const float* logits, float* out) {
+static int softmax7(const float* logits, float* out, int nan_max) {
   float max = -INFINITY;
-  for (int i = 0; i < 7; i++) max = rust_f32_max(max, logits[i]);
+  for (int i = 0; i < 7; i++) max = nan_max ? nan_propagating_max(max, logits[i]) : rust_f32_max(max, logits[i]);
   if (isinf(max)) return C4O_ERR_DEGENERATE_POLICY; /* reference panics */
   float exps[7];
   for (int i = 0; i < 7; i++) exps[i] = c4o_expf(logits[i] - max);
@@ -363,6 +369,8 @@ int c4o_softmax7(const float* logits, float* out) {
   for (int i = 0; i < 7; i++) out[i] = exps[i] / sum;
   return C4O_OK;
 }
+
+int c4o_softmax7(const float* logits, float* out) { return softmax7(logits, out, 0); }
 
 /* mcts.rs:439-454 */
 void c4o_apply_temperature(const float* policy, float t, float* out) {
@@ -675,6 +683,8 @@ struct c4o_game {
   float dir_alpha, dir_eps; /* Dirichlet root noise (extension); eps == 0 disables */
   uint64_t last_select_levels; /* levels of the last select_new_leaf: the depth of g->leaf below the root */
   int prev_step_moved;         /* the last c4o_game_step call made a move */
+  int device_order;            /* c4o_game_set_device_order */
+  unsigned twin;               /* c4o_game_set_twin */
   c4o_counters ctr;
 };
 
@@ -714,6 +724,9 @@ void c4o_game_set_dirichlet(c4o_game* g, float alpha, float epsilon) {
   g->dir_alpha = alpha;
   g->dir_eps = epsilon;
 }
+
+void c4o_game_set_device_order(c4o_game* g, int on) { g->device_order = on; }
+void c4o_game_set_twin(c4o_game* g, unsigned flags) { g->twin = flags; }
 
 void c4o_game_free(c4o_game* g) {
   if (!g) return;
@@ -814,6 +827,7 @@ static void select_new_leaf(c4o_game* g, float c_exploration) {
       if (c < 0) continue;
       float score = node_uct_value(g, &g->nodes[c], c_exploration);
       if (best < 0) {
+        if ((g->twin & C4O_TWIN_NAN_SINGLE) && score != score) { g->error = C4O_ERR_NAN_IN_TREE; g->leaf = idx; return; }
         best = c;
         best_score = score;
       } else {
@@ -829,9 +843,10 @@ static void select_new_leaf(c4o_game* g, float c_exploration) {
   g->leaf = idx;
 }
 
-/* mcts.rs:83-108 */
-int c4o_game_on_received_policy(c4o_game* g, const float* logprobs_in, float q_penalty, float q_no_penalty,
-                                float c_exploration, float c_ply_penalty) {
+/* mcts.rs:83-108.  gate_n != 0 (c4o_game_step in the device's order): the select behind the simulation that gives the root
+ * its gate_n visits is left out -- the gate moves or ends the game, and nobody consumes that leaf. */
+static int on_received_policy(c4o_game* g, const float* logprobs_in, float q_penalty, float q_no_penalty,
+                              float c_exploration, float c_ply_penalty, uint64_t gate_n) {
   if (g->error) return g->error;
   c4o_pos leaf_pos = g->nodes[g->leaf].pos;
   float tq_pen, tq_nopen;
@@ -844,19 +859,32 @@ int c4o_game_on_received_policy(c4o_game* g, const float* logprobs_in, float q_p
     if (depth >= 16) g->ctr.sims_deep_terminal++;
     if (is_root) g->ctr.sims_terminal_root++;
     backpropagate_value(g, tq_pen, tq_nopen, !is_root);
-    select_new_leaf(g, c_exploration);
   } else {
     float logits[7], probs[7];
     memcpy(logits, logprobs_in, sizeof logits);
-    c4o_mask_policy(&leaf_pos, logits);
-    int e = c4o_softmax7(logits, probs);
+    if (!(g->twin & C4O_TWIN_NO_MASK)) c4o_mask_policy(&leaf_pos, logits);
+    int e = softmax7(logits, probs, (g->twin & C4O_TWIN_NAN_MAX) != 0);
     if (e) { g->error = e; return e; }
     expand_leaf(g, probs);
     if (g->leaf == g->root) apply_root_noise(g); /* extension: a root expanded only now */
     backpropagate_value(g, q_penalty, q_no_penalty, 1);
-    select_new_leaf(g, c_exploration);
   }
+  if (gate_n != 0 && g->nodes[g->root].visit_count >= gate_n) {
+    g->last_select_levels = 0; /* no select: nothing to discard */
+    return g->error;
+  }
+  select_new_leaf(g, c_exploration);
   return g->error;
+}
+
+int c4o_game_on_received_policy(c4o_game* g, const float* logprobs_in, float q_penalty, float q_no_penalty,
+                                float c_exploration, float c_ply_penalty) {
+  return on_received_policy(g, logprobs_in, q_penalty, q_no_penalty, c_exploration, c_ply_penalty, 0);
+}
+
+int c4o_game_on_received_policy_gated(c4o_game* g, const float* logprobs_in, float q_penalty, float q_no_penalty,
+                                      float c_exploration, float c_ply_penalty, uint64_t gate_n) {
+  return on_received_policy(g, logprobs_in, q_penalty, q_no_penalty, c_exploration, c_ply_penalty, gate_n);
 }
 
 /* mcts.rs:396-412 */
@@ -981,7 +1009,7 @@ int c4o_game_to_result(const c4o_game* g, float c_ply_penalty, c4o_sample* out, 
 /* self_play.rs:268-323  one MctsJob::Job */
 int c4o_game_step(c4o_game* g, const float* logprobs7, float q_pen, float q_nopen,
                   uint64_t n_mcts_iterations, float c_exploration, float c_ply_penalty) {
-  int e = c4o_game_on_received_policy(g, logprobs7, q_pen, q_nopen, c_exploration, c_ply_penalty);
+  int e = on_received_policy(g, logprobs7, q_pen, q_nopen, c_exploration, c_ply_penalty, g->device_order ? n_mcts_iterations : 0);
   if (e) return -e;
   if (c4o_game_root_visit_count(g) < n_mcts_iterations) { g->prev_step_moved = 0; return 0; } /* self_play.rs:283-286 */
   g->ctr.select_levels_discarded += g->last_select_levels;

@@ -139,8 +139,25 @@ void c4o_game_leaf_pos(const c4o_game* g, c4o_pos* out);
 uint64_t c4o_game_leaf_model_id(const c4o_game* g);                      /* mcts.rs:70-76 */
 int c4o_game_on_received_policy(c4o_game* g, const float* logprobs7, float q_pen, float q_nopen,
                                 float c_exploration, float c_ply_penalty); /* mcts.rs:83-108 */
+/* the same without the select once the root has gate_n visits (0 = always select): a SEARCH in the device's order -- the slot is
+ * handed on behind the search's last simulation, and the select run_mcts would still make (mcts.rs:469-485) is left out */
+int c4o_game_on_received_policy_gated(c4o_game* g, const float* logprobs7, float q_pen, float q_nopen,
+                                      float c_exploration, float c_ply_penalty, uint64_t gate_n);
 int c4o_game_make_move(c4o_game* g, int col, float c_exploration);       /* mcts.rs:187-206 */
 int c4o_game_make_random_move(c4o_game* g, float c_exploration, float temperature); /* mcts.rs:214-222 */
+/* TEST SWITCHES of one game (both off in a new game: the reference's rules in the reference's order).
+ * c4o_game_set_device_order(g, 1): c4o_game_step plays the DEVICE'S order of a job -- expand, back up, then the gate; the select
+ * behind the simulation that gives the root its n visits is left out, where the reference runs it and throws its leaf away
+ * (select_levels_discarded; the move's own select follows from the new root either way).  Samples cannot differ; panics can: a
+ * NaN that this select alone would compare goes unseen (the fourth counted deviation).  n_mcts_iterations == 0
+ * keeps the reference's order.  c4o_game_on_received_policy is unchanged by it.
+ * c4o_game_set_twin(g, flags): MUTANTS of three of the reference's rules, for tests that show a job can see such a bug
+ * (tests/test_nonfinite_regime.py): C4O_TWIN_NO_MASK = illegal columns are not masked before the softmax (c4r.rs:272-286 skipped),
+ * C4O_TWIN_NAN_SINGLE = a NaN score panics although it is the only candidate (utils.rs:12 compares two keys),
+ * C4O_TWIN_NAN_MAX = the softmax's maximum propagates a NaN where f32::max ignores it (mcts.rs:417-419). */
+enum { C4O_TWIN_NO_MASK = 1, C4O_TWIN_NAN_SINGLE = 2, C4O_TWIN_NAN_MAX = 4 };
+void c4o_game_set_device_order(c4o_game* g, int on);
+void c4o_game_set_twin(c4o_game* g, unsigned flags);
 uint64_t c4o_game_root_visit_count(const c4o_game* g);                    /* mcts.rs:248-250 */
 void c4o_game_root_policy(const c4o_game* g, float* out7);                /* mcts.rs:254-256 */
 float c4o_game_root_q_penalty(const c4o_game* g);                         /* mcts.rs:260-262 */

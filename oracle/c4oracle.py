@@ -135,12 +135,15 @@ def lib() -> C.CDLL:
         "c4o_shuffle_games": (C.c_int, [C.c_uint64, C.c_uint64, P(C.c_uint32)]),
         "c4o_self_play_set_dirichlet": (None, [C.c_float, C.c_float]),
         "c4o_game_set_dirichlet": (None, [C.c_void_p, C.c_float, C.c_float]),
+        "c4o_game_set_device_order": (None, [C.c_void_p, C.c_int]),
+        "c4o_game_set_twin": (None, [C.c_void_p, C.c_uint]),
         "c4o_game_new": (C.c_void_p, [P(Pos), C.c_uint64, C.c_uint64, C.c_uint64]),
         "c4o_game_free": (None, [C.c_void_p]),
         "c4o_game_root_pos": (None, [C.c_void_p, P(Pos)]),
         "c4o_game_leaf_pos": (None, [C.c_void_p, P(Pos)]),
         "c4o_game_leaf_model_id": (C.c_uint64, [C.c_void_p]),
         "c4o_game_on_received_policy": (C.c_int, [C.c_void_p, f32p, C.c_float, C.c_float, C.c_float, C.c_float]),
+        "c4o_game_on_received_policy_gated": (C.c_int, [C.c_void_p, f32p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64]),
         "c4o_game_make_move": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
         "c4o_game_make_random_move": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
         "c4o_game_root_visit_count": (C.c_uint64, [C.c_void_p]),
@@ -348,6 +351,10 @@ def sharp_eval_batch(planes: np.ndarray, k: int, q_mode: str, ties: bool):
     return lp, qp, qn, {"rows": int(ctx.rows), "rows_used": int(ctx.rows_used), "rows_zero_prior": int(ctx.rows_zero_prior), "rows_subnormal_prior": int(ctx.rows_subnormal_prior)}
 
 
+TWIN_NO_MASK, TWIN_NAN_SINGLE, TWIN_NAN_MAX = 1, 2, 4
+ERR_NAN_IN_TREE, ERR_DEGENERATE_POLICY, ERR_ILLEGAL_MOVE = 1, 2, 3
+
+
 class Game:
     """One MctsGame (mcts.rs:27-32)."""
 
@@ -361,7 +368,21 @@ class Game:
             self._L.c4o_game_free(self._g)
             self._g = None
 
-    def on_received_policy(self, logprobs, q_pen, q_nopen, c_exploration, c_ply_penalty) -> int:
+    def set_dirichlet(self, alpha: float, epsilon: float) -> None:
+        self._L.c4o_game_set_dirichlet(self._g, float(alpha), float(epsilon))
+
+    def set_device_order(self, on: bool = True) -> None:
+        """step() leaves out the select behind the simulation that completes the root's n visits, as the device does (c4_oracle.h)"""
+        self._L.c4o_game_set_device_order(self._g, int(bool(on)))
+
+    def set_twin(self, flags: int) -> None:
+        """mutants of the reference's rules, TWIN_* (c4_oracle.h c4o_game_set_twin)"""
+        self._L.c4o_game_set_twin(self._g, int(flags))
+
+    def on_received_policy(self, logprobs, q_pen, q_nopen, c_exploration, c_ply_penalty, gate_n: int = 0) -> int:
+        """gate_n > 0: no select once the root has gate_n visits (a search in the device's order, c4_oracle.h)"""
+        if gate_n:
+            return self._L.c4o_game_on_received_policy_gated(self._g, _f7(logprobs), q_pen, q_nopen, c_exploration, c_ply_penalty, gate_n)
         return self._L.c4o_game_on_received_policy(self._g, _f7(logprobs), q_pen, q_nopen, c_exploration, c_ply_penalty)
 
     def step(self, logprobs, q_pen, q_nopen, n_iter, c_exploration, c_ply_penalty) -> int:

@@ -79,6 +79,61 @@ def start_job_search(ev_name, n):
     return _JOBS[key]
 
 
+POISON_SEARCH_RATE = 40   # 21 errored searches of 495 at n = 8, 52 at n = 24: under half of the 128 slots (an errored slot stays dead)
+_POISON = {}
+
+
+def poison_search(n, rate, device_order=False):
+    """tests.helpers.start_job's 495 positions searched under the hash evaluator poisoned at one position in `rate`
+    (tests.helpers.poison_eval_np), every search alone, all in lock-step.  Per position ("ok", policy float32[7], q_penalty,
+    q_no_penalty as float32) or (code, where): the C4O_ERR code of the reference's panic, where = "live" | "discarded" -- discarded =
+    raised by the select behind the search's LAST simulation, which run_mcts (mcts.rs:469-485) makes and nobody consumes.
+    device_order: that select is left out, as the device hands the slot on instead (c4o_game_on_received_policy_gated): such a
+    search finishes, and its record may carry a NaN root q.  Also returns the number of evaluator rows."""
+    key = (n, rate, bool(device_order))
+    if key not in _POISON:
+        from oracle import c4oracle as O
+        from tests.helpers import hash_eval_np, poison_eval_np, pos_to_planes_np
+
+        _reqs, starts, _part = start_job()
+        ev = poison_eval_np(hash_eval_np, rate)
+        games = [O.Game(O.Pos(int(m), int(v))) for m, v in starts]
+        out, live, rows = [None] * len(games), list(range(len(games))), 0
+        for it in range(n):
+            leaves = [games[i].leaf_pos() for i in live]
+            lg, qp, qn = ev(0, pos_to_planes_np(np.array([p.mask for p in leaves], np.uint64), np.array([p.value for p in leaves], np.uint64)))
+            rows += len(live)
+            nxt = []
+            for j, i in enumerate(live):
+                err = games[i].on_received_policy(lg[j], float(qp[j]), float(qn[j]), START_EVALS["hash"][1], C_PLY_PENALTY, gate_n=n if device_order else 0)
+                if err:
+                    out[i] = (err, "discarded" if it == n - 1 and err == O.ERR_NAN_IN_TREE else "live")
+                else:
+                    nxt.append(i)
+            live = nxt
+        for i in live:
+            g = games[i]
+            out[i] = ("ok", g.root_policy().astype(np.float32), np.float32(g.root_q_penalty()), np.float32(g.root_q_no_penalty()))
+        _POISON[key] = (out, rows)
+    return _POISON[key]
+
+
+def same_search_outcome(a, b):
+    """two outcomes of poison_search agree: the same code, or the same record under the record rule below"""
+    if a[0] != "ok" or b[0] != "ok":
+        return a[0] == b[0]
+    return all(_same_f32(x, y) for x, y in zip(a[1:], b[1:]))
+
+
+def _same_f32(x, y):
+    """THE RECORD RULE of the non-finite tier: a NaN equals a NaN, everything else bit for bit.  IEEE 754 leaves the payload and
+    the sign of a NaN that comes out of an addition or a division to the implementation, and x86 and the GPU may differ; no other
+    relaxation, and no position is left out."""
+    x, y = np.atleast_1d(np.asarray(x, np.float32)), np.atleast_1d(np.asarray(y, np.float32))
+    nan = np.isnan(x)
+    return bool(np.array_equal(nan, np.isnan(y)) and np.array_equal(x[~nan].view(np.uint32), y[~nan].view(np.uint32)))
+
+
 def long_search_positions(k=16):
     """the first k non-terminal random starts of the job (T2: long searches)"""
     from oracle import c4oracle as O

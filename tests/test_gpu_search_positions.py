@@ -9,7 +9,13 @@ comparison is tests/search_ref.py; tests/test_search_positions.py holds that fix
   T3  a bf16 network through every driver -- the library's own loop (c4_search_positions_bf16) and the Python loop, one and two
       sessions, few and many slots, records left on the device -- the same bytes, equal to oracle games driven in lock-step with
       the same network's answers; once with the f32 chain;
-  T4  every refusal, and the session / process works afterwards.
+  T4  every refusal, and the session / process works afterwards;
+  T5  non-finite evaluator outputs (tests.search_ref.poison_search: the hash evaluator poisoned at one position in 40, n = 8 and
+      24): per position the reference's panic code in the slot's status byte, or the one record.  Here non-finite values DO reach
+      records -- a NaN root q where the reference finishes the search, e.g. down a chain of single legal columns, and a NaN
+      q_no_penalty, which is never compared -- so records are compared by the record rule of tests/search_ref.py: a NaN equals a
+      NaN, everything else bit for bit.  The oracle plays the device's order: the select behind a search's last simulation is left
+      out (the fourth counted deviation; tests/test_nonfinite_regime.py pins which searches that changes).
 
 Without the feature every test here fails at `search=True` or at the import of `search_positions`."""
 import ctypes as C
@@ -22,8 +28,8 @@ torch = pytest.importorskip("torch")
 
 from tests.helpers import (N_START_SLOTS, SHARP_MODEL_K, START_EVALS, GraphSafeHashEval, GraphSafeSharpEval, evidence, hash_eval_torch,   # noqa: E402
                            sharp_eval_torch, sharp_model, start_job)
-from tests.search_ref import (C_PLY_PENALTY, assert_counters, assert_records_equal, long_search_positions, oracle_evaluator, search,   # noqa: E402
-                              start_job_search)
+from tests.search_ref import (C_PLY_PENALTY, POISON_SEARCH_RATE, assert_counters, assert_records_equal, long_search_positions,   # noqa: E402
+                              oracle_evaluator, poison_search, same_search_outcome, search, start_job_search)
 
 DEV = "cuda:0"
 
@@ -297,3 +303,54 @@ def test_native_and_api_refusals_leave_the_process_usable():
     assert_records_equal(h.records, search(positions, 24, oracle_evaluator("hash"), 6.6), positions)
     games_after = c4a0_amd.play_games([c4a0_amd.GameMetadata(i, 0, 0) for i in range(8)], 64, 8, 6.6, 0.01, evaluator=net)
     assert len(games_after) == 8
+
+
+# --------------------------------------------------------------------------------------------- T5
+T5_JOBS = [("poison-n8-f32-eager", 8, "f32", {}), ("poison-n24-bf16-graph4", 24, "bf16", {"graph": 4}), ("poison-n8-bf16-graph4", 8, "bf16", {"graph": 4})]
+
+
+@pytest.mark.parametrize("job", T5_JOBS, ids=[j[0] for j in T5_JOBS])
+def test_poisoned_searches_end_as_the_oracle_says(job):
+    """stepped by hand until no slot is active (run() raises at its first poll); per position the status byte or the record"""
+    from tests.helpers import (C4_OF_C4O, GraphSafePoisonEval, poison_eval_torch, step_eager_until_no_slot_is_active as _step_eager,
+                               step_graph_until_no_slot_is_active as _step_graph)
+
+    name, n, planes, opt = job
+    _reqs, starts, _part = start_job()
+    want, rows = poison_search(n, POISON_SEARCH_RATE, device_order=True)
+    ref, _rows = poison_search(n, POISON_SEARCH_RATE)
+    s = _search_session(N_START_SLOTS, n, START_EVALS["hash"][1], planes)
+    s.set_games(_requests(len(starts)), starts)
+    s.bind()
+    s.start()
+    dead, where = {}, {}
+    if "graph" in opt:
+        steps = _step_graph(s, GraphSafePoisonEval(hash_eval_torch, POISON_SEARCH_RATE), opt["graph"], rows, dead, where)
+    else:
+        steps = _step_eager(s, poison_eval_torch(hash_eval_torch, POISON_SEARCH_RATE), rows, dead, where)
+    recs, counts, c = s.drain_samples(), s.sample_counts(), s.counters()
+    s.close()
+    by_id = {int(r["game_id"]): r for r in recs}
+    assert len(by_id) == len(recs)
+    bad, nan_q, nan_qn = [], 0, 0
+    for i, (o, pos) in enumerate(zip(want, starts)):
+        if o[0] == "ok":
+            r = by_id.get(i)
+            if r is None or i in dead or counts[i] != 1 or (int(r["mask"]), int(r["value"])) != pos or r["meta"] != 2 << 16 or \
+                    not same_search_outcome(("ok", r["policy"], r["q_penalty"], r["q_no_penalty"]), o):
+                bad.append((i, "finished", dead.get(i, "record differs")))
+            nan_q += bool(np.isnan(o[2]))
+            nan_qn += bool(np.isnan(o[3]))
+        elif dead.get(i) != C4_OF_C4O[o[0]] or i in by_id or counts[i] != 0:
+            bad.append((i, o, dead.get(i, "finished")))
+    escaped = [i for i, (a, b) in enumerate(zip(ref, want)) if not same_search_outcome(a, b)]
+    print(f"{name}: device error {c['error']} at slot {c['error_slot']}, {len(dead)} dead, escaped in the device's order {escaped}: on the device "
+          f"{[dead.get(i, 'finished') for i in escaped]}")
+    assert not bad, f"{len(bad)} searches differ from the oracle, first {bad[:5]}"
+    n_ok = sum(1 for o in want if o[0] == "ok")
+    assert len(dead) == len(starts) - n_ok and c["games_done"] == n_ok == len(recs)
+    assert c["error"] in set(dead.values()) and c["error_slot"] in {where[o] for o, code in dead.items() if code == c["error"]}
+    assert nan_q >= 1 and nan_qn >= 1
+    evidence(f"search T5 {name}: {len(starts)} positions: {n_ok} records == oracle (a NaN equals a NaN, else bit for bit; {nan_q} with a NaN "
+             f"root q, {nan_qn} with a NaN q_no_penalty), {len(dead)} dead slots == the oracle's panic codes, {len(escaped)} searches escape "
+             f"the reference's panic behind the last simulation, {steps} steps")
