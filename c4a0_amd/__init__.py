@@ -14,6 +14,9 @@ def __getattr__(name):  # torch / the HIP library are loaded on first use of the
     if name in ("play_games", "search_positions", "run_tui", "DeviceCallback", "trim_cached_memory"):
         from . import api
         return getattr(api, name)
+    if name == "Engine":   # GPU-resident interactive play: games whose trees persist across moves from outside
+        from .engine import Engine
+        return Engine
     if name == "SearchResult":
         from .results import SearchResult
         return SearchResult

@@ -21,8 +21,13 @@ FLAG_ONE_SIM_PER_STEP = 2
 FLAG_RECLAIM = 4          # include/c4a0_hip.h C4_FLAG_RECLAIM: the tree arena is reclaimed while a game is played
 FLAG_NO_RECLAIM = 8       # ... never, also where the default sizing would
 FLAG_SEARCH = 16          # include/c4a0_hip.h C4_FLAG_SEARCH: every request is one search of its start position (one record), not a game
+FLAG_HOLD = 32            # include/c4a0_hip.h C4_FLAG_HOLD: every request is one persistent game, searched to a target and moved from outside
+HOLD_PARKED = 64          # ... the slot status of a parked game
+HOLD_MOVE_NONE, HOLD_MOVE_SAMPLE = -1, -2   # c4_session_hold_resume: a slot's move (or a column 0..6) ...
+HOLD_OK, HOLD_REFUSED_TERMINAL, HOLD_REFUSED_COLUMN, HOLD_REFUSED_UNSEARCHED, HOLD_REFUSED_SAMPLE, HOLD_NO_GAME = range(6)   # ... and its result
+HOLD_POLL_UNKNOWN = 0xFFFFFFFF
 MAX_SAMPLES_PER_GAME = 43
-ABI_VERSION = 12   # include/c4a0_hip.h C4_ABI_VERSION: the signatures below are that version's
+ABI_VERSION = 13   # include/c4a0_hip.h C4_ABI_VERSION: the signatures below are that version's
 STRUCT_LAYOUT_SINCE = 7   # the ABI version that last changed a structure's layout (c4_config.reclaim_period, c4_counters.reclaim_*)
 
 
@@ -127,6 +132,10 @@ SIGNATURES = {
     "c4_session_unique_leaves": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "c4_session_scatter_outputs": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "c4_session_step_gather": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
+    "c4_session_set_iterations": (C.c_int, [_vp, C.c_uint32]),
+    "c4_session_hold_resume": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "c4_session_snapshot": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64]),
+    "c4_session_hold_poll": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "c4_session_leaves": (C.c_int, [_vp, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint32)]),
     "c4_pos_ops": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c4_encode_planes": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp]),

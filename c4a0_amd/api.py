@@ -531,5 +531,8 @@ class DeviceCallback:
 
 
 def run_tui(*_a, **_k):
-    """reference pybridge.rs:231-251: terminal UI -- out of scope."""
-    raise NotImplementedError("run_tui (interactive terminal UI) is out of scope of the self-play generator")
+    """reference pybridge.rs:231-251: terminal UI -- out of scope.  The engine such a UI would sit on is here: `c4a0_amd.Engine`
+    (c4a0_amd/engine.py) is the reference's `InteractivePlay` (rust/src/interactive_play.rs) -- a tree that lives on across
+    `make_moves`, `search` up to a visit target, `add_iterations`, `snapshot` -- for any number of games at once."""
+    raise NotImplementedError("run_tui (interactive terminal UI) is out of scope of the self-play generator; the engine a UI would sit on is "
+                              "c4a0_amd.Engine (make_moves / make_random_moves / search / add_iterations / snapshot)")

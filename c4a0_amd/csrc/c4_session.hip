@@ -98,7 +98,7 @@ C4_DEV constexpr uint32_t slot_state(uint32_t status, uint32_t depth, uint32_t n
 C4_DEV uint32_t slot_status(uint32_t state) { return state & 0xFFu; }
 static_assert(sizeof(Block) == 128 && sizeof(Entry) == 16 && sizeof(Tail) == 16 && sizeof(c4_sample_rec) == 64, "layout");
 
-enum : uint32_t { kIdle = 0, kActive = 1 };
+enum : uint32_t { kIdle = 0, kActive = 1, kParked = C4_HOLD_PARKED };   // (kParked: hold sessions only, a status of its own)
 constexpr uint32_t kWavesPerTimingHelper = 1024;   // stamps one timing helper workgroup reduces
 
 // Diagnostic build only (-DC4_PHASE_STAMPS, tools/phase_profile.py): per-wavefront device-clock
@@ -127,6 +127,8 @@ struct Globals {             // one small device struct of cross-wave words
   unsigned long long games_done;
   uint32_t error;            // first error status
   uint32_t error_slot;
+  uint32_t hold_active;      // hold sessions (C4_FLAG_HOLD): slots whose status is active
+  uint32_t hold_need;        // ... and the largest n_iter - root visits among them at the last c4_session_hold_resume
 };
 
 struct Params {
@@ -163,6 +165,12 @@ struct Params {
   uint32_t n_ln;
   uint32_t half_blocks;           // reclaimed arenas (C4_FLAG_RECLAIM): blocks per half, blocks_per_slot = 2 x this; 0 = never-reclaimed arena
   unsigned long long* reclaim_ctr;   // [2] passes, blocks copied (k_arena_reclaim)
+  // hold sessions (C4_FLAG_HOLD), read by k_hold_resume alone: per-slot moves (null = none), their temperatures, where the
+  // per-slot result codes go (may be null), and whether the launch is c4_session_start's (the slots were reset just now)
+  const int32_t* hold_cols;
+  const float* hold_temps;
+  int32_t* hold_results;
+  uint32_t hold_fresh;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -493,7 +501,15 @@ C4_DEV void timing_helper(const Params& p, uint32_t lane) {
 // start position (mcts.rs:48-56 new_from_pos + the run_mcts helper, mcts.rs:469-485; interactive_play.rs:33, 57).  A terminal root is
 // searched like any other, the gate writes one record -- root policy and root q -- instead of moving, and the slot takes the next
 // request; no temperature, no move RNG.
-template <typename PlaneT, bool NOISE, bool CACHE, bool SEARCH = false>
+// HOLD (C4_FLAG_HOLD, an instantiation of its own too): every slot keeps ONE game whose tree persists across moves
+// (interactive_play.rs: InteractivePlay around one MctsGame).  The gate follows State::bg_thread_should_stop
+// (interactive_play.rs:188-191): a game whose root has n_iter visits after expand + backup is PARKED -- status kParked, no select,
+// no planes, no move, no record -- and skipped by every later step; nothing is ever refilled.
+// RESUME (with HOLD; k_hold_resume, the one place where a game becomes active): the first trip has no evaluator answer to consume.
+// It starts at the gate, with an optional move from outside (InteractivePlay::make_move / make_random_move,
+// interactive_play.rs:70-85, 169-185: the self-play gate's own record / re-root / finish code, the column and the temperature given
+// per slot, a refusal instead of a panic), parks or selects, and goes on as any trip does.
+template <typename PlaneT, bool NOISE, bool CACHE, bool SEARCH = false, bool HOLD = false, bool RESUME = false>
 C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t lane, const uint32_t n_slots, Slot* st, const uint4 hot,
                       const float nn_logit, const float nn_q, const unsigned long long t_start, const uint32_t g) {
   // g = this lane group's game (>= n_slots: none).  The stand-alone kernels give a wavefront the 8 games 8 wave_index .. + 7; the fused
@@ -505,6 +521,21 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
   // header words to every lane of the group (lane 3: state, arena, root ref, rng word)
   const uint32_t state0 = shfl_u32(hot.x, gbase + 3);
   bool active = (g < n_slots) && (slot_status(state0) == kActive);
+  // hold sessions: was the slot active when the launch began (a slot c4_session_start has just reset counts as new), is it parked
+  // by this launch, does a refused move / a search already under way leave it exactly as it is; the move asked of it from outside
+  const bool was_active = HOLD && active && !(RESUME && p.hold_fresh);
+  bool park = false, untouched = false;
+  int32_t mv = C4_HOLD_MOVE_NONE;
+  float mv_temp = 1.0f;
+  if (RESUME) {
+    active = (g < n_slots) && (slot_status(state0) == kActive || slot_status(state0) == kParked);
+    if (g < n_slots && p.hold_cols) {
+      mv = p.hold_cols[g];
+      mv_temp = p.hold_temps ? p.hold_temps[g] : 1.0f;
+      // (a slot without a live game -- never given one, or ended by a device error -- has nothing to move)
+      if (sub == 0 && p.hold_results) p.hold_results[g] = (mv != C4_HOLD_MOVE_NONE && !active) ? C4_HOLD_NO_GAME : C4_HOLD_OK;
+    }
+  }
   uint4 line = hot;          // what goes back to the slot at the end
   bool store_line = false;
   // move RNG precompute (see the end of the kernel): what this game will need at its next move
@@ -535,7 +566,7 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
     uint32_t leaf_ref = path_level(pv, st, depth, gbase);   // the waiting leaf's own entry
     bool fresh = false;                  // the slot took a new game in this launch
     uint32_t err = 0;
-    uint32_t root_n = 0;
+    uint32_t root_n = RESUME ? shfl_u32(hot.w, gbase + 2) : 0u;   // (a resumed game: the slot's mirror of the root's visit count)
     // One simulation per game per launch, plus a second one when the leaf just selected is terminal:
     // such a leaf needs no evaluator row (mcts.rs:92-98 ignores the network for it), so its value is
     // backed up here and now instead of idling through an evaluator pass.  The order of a game's
@@ -557,86 +588,89 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
       // (self_play.rs:283-308, mcts.rs:271-313): as after a move into a terminal position, the game is closed now and the
       // simulations are counted as skipped.  (C4_FLAG_NO_MOVES, the reference's run_mcts, keeps searching such a root.)
       // (A search keeps searching it too: its root q is q_sum / (n + 1), not the terminal value.)
-      const bool term_start = !SEARCH && term != 0 && depth == 0 && !(p.flags & C4_FLAG_NO_MOVES);
-      // ---------------- on_received_policy: terminal value or expansion -------------------
+      // (A hold session never searches a terminal root: it is parked from the start, or from the move that made it terminal.)
+      const bool term_start = !SEARCH && !HOLD && term != 0 && depth == 0 && !(p.flags & C4_FLAG_NO_MOVES);
       float v_pen, v_nopen;
-      if (term) {
-        c4::terminal_value(term, leaf_mask, p.c_ply_penalty, v_pen, v_nopen);  // NN output ignored (mcts.rs:92-98)
-      } else {
-        // first simulation: the network's outputs; a later one gets here only on an evaluation-cache hit
-        const uint32_t legal = c4::legal_mask(leaf_mask);
-        const bool is_legal = sub < 7 && ((legal >> sub) & 1u);
-        float logit = __uint_as_float(0xff800000u);                             // mask_policy, c4r.rs:272-286
-        if (is_legal) logit = cur_logit;
-        float mx = logit;                                                       // f32::max fold (NaN-ignoring)
-        mx = c4::rust_max(mx, grp_xchg<0>(mx));
-        mx = c4::rust_max(mx, grp_xchg<1>(mx));
-        mx = c4::rust_max(mx, grp_xchg<2>(mx));
-        if (__builtin_isinf(mx)) err = C4_ERR_DEGENERATE_POLICY;                // mcts.rs:421-425
-        const float ex = c4::c4_expf(logit - mx);
-        float sum = 0.0f;                                                       // left-to-right, mcts.rs:432
-        for (int i = 0; i < 7; i++) sum = sum + shfl_f32(ex, gbase + i);
-        float prior = ex / sum;
-        if (NOISE && p.dir_eps > 0.0f && depth == 0) {
-          // extension: the root is expanded only now -> its children start with noisy priors
-          float eta[7];
-          c4::dirichlet_noise(game_id, n_moves, legal, p.dir_alpha, eta);
-          float mine = eta[0];
-          for (int c = 1; c < 7; c++) mine = (sub == (uint32_t)c) ? eta[c] : mine;
-          if (is_legal) {
-            const float keep = (1.0f - p.dir_eps) * prior;
-            const float add = p.dir_eps * mine;
-            prior = keep + add;
+      if (!(RESUME && sim == 0)) {   // (a resumed game's first trip has no answer to consume: it starts at the gate)
+        // ---------------- on_received_policy: terminal value or expansion -------------------
+        if (term) {
+          c4::terminal_value(term, leaf_mask, p.c_ply_penalty, v_pen, v_nopen);  // NN output ignored (mcts.rs:92-98)
+        } else {
+          // first simulation: the network's outputs; a later one gets here only on an evaluation-cache hit
+          const uint32_t legal = c4::legal_mask(leaf_mask);
+          const bool is_legal = sub < 7 && ((legal >> sub) & 1u);
+          float logit = __uint_as_float(0xff800000u);                             // mask_policy, c4r.rs:272-286
+          if (is_legal) logit = cur_logit;
+          float mx = logit;                                                       // f32::max fold (NaN-ignoring)
+          mx = c4::rust_max(mx, grp_xchg<0>(mx));
+          mx = c4::rust_max(mx, grp_xchg<1>(mx));
+          mx = c4::rust_max(mx, grp_xchg<2>(mx));
+          if (__builtin_isinf(mx)) err = C4_ERR_DEGENERATE_POLICY;                // mcts.rs:421-425
+          const float ex = c4::c4_expf(logit - mx);
+          float sum = 0.0f;                                                       // left-to-right, mcts.rs:432
+          for (int i = 0; i < 7; i++) sum = sum + shfl_f32(ex, gbase + i);
+          float prior = ex / sum;
+          if (NOISE && p.dir_eps > 0.0f && depth == 0) {
+            // extension: the root is expanded only now -> its children start with noisy priors
+            float eta[7];
+            c4::dirichlet_noise(game_id, n_moves, legal, p.dir_alpha, eta);
+            float mine = eta[0];
+            for (int c = 1; c < 7; c++) mine = (sub == (uint32_t)c) ? eta[c] : mine;
+            if (is_legal) {
+              const float keep = (1.0f - p.dir_eps) * prior;
+              const float add = p.dir_eps * mine;
+              prior = keep + add;
+            }
+          }
+          const uint32_t nb = n_blocks;
+          // (a reclaimed arena is two halves: the bump pointer of the lower one stops at the boundary; half_blocks == 0 otherwise, never a block number)
+          if (nb >= p.blocks_per_slot || nb == p.half_blocks) err = err ? err : C4_ERR_ARENA_OVERFLOW;
+          if (!err) {
+            // Node::new (mcts.rs:345-355) for the 7 children; lane 7 writes the tail (no links yet)
+            reinterpret_cast<uint4*>(blocks + nb)[sub] =
+                sub < 7 ? make_uint4(0u, 0u, 0u, __float_as_uint(prior)) : make_uint4(0u, 0u, 0u, legal << 16);
+            if (sub == 0) blocks[leaf_ref >> 3].t.child[leaf_ref & 7] = (uint16_t)nb;   // leaf.children = Some(..)
+            if (depth == 0) root_block = nb;
+            n_blocks = nb + 1;
+            c_E += 1;
+          }
+          v_pen = cur_qp;
+          v_nopen = cur_qn;
+          if (CACHE && sim == 0)     // extension: remember what the evaluator said about this position
+            cache_store(p.cache, p.cache_mask, leaf_mask, leaf_value, nn_logit, cur_qp, cur_qn, sub, gbase);
+        }
+        if (err) break;
+
+        C4_STAMP_TRIP1(2, n_blocks);
+        // ---------------- backpropagate_value: leaf -> root along the recorded path ----------
+        root_n = 0;
+        if (sub >= 4) {   // level d on lane 4 + (d & 3): the first four levels update in parallel
+          for (uint32_t d = sub - 4; d <= depth; d += 4) {
+            const uint32_t c = d >> 2;
+            const uint32_t ref = c == 0 ? pv.x : (c == 1 ? pv.y : (c == 2 ? pv.z : (c == 3 ? pv.w : st->path_deep[d - kHotPath])));
+            Entry* e = &blocks[ref >> 3].e[ref & 7];
+            const bool odd = ((depth - d) & 1u) != 0;                             // value negated per step up
+            const uint32_t n1 = e->n + 1;
+            const float q1 = e->q_pen + (odd ? -v_pen : v_pen);
+            const float q2 = e->q_nopen + (odd ? -v_nopen : v_nopen);
+            e->n = n1;
+            e->q_pen = q1;
+            e->q_nopen = q2;
+            if (d == 0) root_n = n1;
           }
         }
-        const uint32_t nb = n_blocks;
-        // (a reclaimed arena is two halves: the bump pointer of the lower one stops at the boundary; half_blocks == 0 otherwise, never a block number)
-        if (nb >= p.blocks_per_slot || nb == p.half_blocks) err = err ? err : C4_ERR_ARENA_OVERFLOW;
-        if (!err) {
-          // Node::new (mcts.rs:345-355) for the 7 children; lane 7 writes the tail (no links yet)
-          reinterpret_cast<uint4*>(blocks + nb)[sub] =
-              sub < 7 ? make_uint4(0u, 0u, 0u, __float_as_uint(prior)) : make_uint4(0u, 0u, 0u, legal << 16);
-          if (sub == 0) blocks[leaf_ref >> 3].t.child[leaf_ref & 7] = (uint16_t)nb;   // leaf.children = Some(..)
-          if (depth == 0) root_block = nb;
-          n_blocks = nb + 1;
-          c_E += 1;
-        }
-        v_pen = cur_qp;
-        v_nopen = cur_qn;
-        if (CACHE && sim == 0)     // extension: remember what the evaluator said about this position
-          cache_store(p.cache, p.cache_mask, leaf_mask, leaf_value, nn_logit, cur_qp, cur_qn, sub, gbase);
+        root_n = shfl_u32(root_n, gbase + 4);
+        c_sims += term_start ? 0u : 1u;
+        // (a search's simulations of a terminal root are not counted in K, as the oracle counts backup_nodes)
+        c_K += (term_start || (SEARCH && term != 0 && depth == 0)) ? 0u : depth + 1;
+        // The stores above are read back below through other lanes of THIS wavefront.  A wavefront's
+        // vector-memory instructions reach the cache in program order, so a later load of the same
+        // address returns the stored bytes without waiting for the store's acknowledgement: only the
+        // compiler must not reorder them (a wavefront-scope fence emits no instruction).
+        C4_STAMP_TRIP1(3, root_n);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        C4_STAMP_TRIP1(4, root_n);
       }
-      if (err) break;
-
-      C4_STAMP_TRIP1(2, n_blocks);
-      // ---------------- backpropagate_value: leaf -> root along the recorded path ----------
-      root_n = 0;
-      if (sub >= 4) {   // level d on lane 4 + (d & 3): the first four levels update in parallel
-        for (uint32_t d = sub - 4; d <= depth; d += 4) {
-          const uint32_t c = d >> 2;
-          const uint32_t ref = c == 0 ? pv.x : (c == 1 ? pv.y : (c == 2 ? pv.z : (c == 3 ? pv.w : st->path_deep[d - kHotPath])));
-          Entry* e = &blocks[ref >> 3].e[ref & 7];
-          const bool odd = ((depth - d) & 1u) != 0;                             // value negated per step up
-          const uint32_t n1 = e->n + 1;
-          const float q1 = e->q_pen + (odd ? -v_pen : v_pen);
-          const float q2 = e->q_nopen + (odd ? -v_nopen : v_nopen);
-          e->n = n1;
-          e->q_pen = q1;
-          e->q_nopen = q2;
-          if (d == 0) root_n = n1;
-        }
-      }
-      root_n = shfl_u32(root_n, gbase + 4);
-      c_sims += term_start ? 0u : 1u;
-      // (a search's simulations of a terminal root are not counted in K, as the oracle counts backup_nodes)
-      c_K += (term_start || (SEARCH && term != 0 && depth == 0)) ? 0u : depth + 1;
-      // The stores above are read back below through other lanes of THIS wavefront.  A wavefront's
-      // vector-memory instructions reach the cache in program order, so a later load of the same
-      // address returns the stored bytes without waiting for the store's acknowledgement: only the
-      // compiler must not reorder them (a wavefront-scope fence emits no instruction).
-      C4_STAMP_TRIP1(3, root_n);
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      C4_STAMP_TRIP1(4, root_n);
 
       // ---------------- gate: self_play.rs:283-308 ------------------------------------------
       bool finished = false;
@@ -665,9 +699,25 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
         c_samples += 1;
         finished = true;
       }
-      if (!SEARCH && ((root_n >= p.n_iter && !(p.flags & C4_FLAG_NO_MOVES)) || term_start)) {
+      // A hold session moves only when asked to from outside, in k_hold_resume's first trip: a given column, or a sampled one at
+      // the slot's temperature.  What the reference answers with `false` or a panic is a REFUSAL here (C4_HOLD_REFUSED_*): a
+      // terminal root (interactive_play.rs:171, 180), a column outside 0-6 or full (:171), a root without children yet
+      // (mcts.rs:196 panics) and a sampled column that is not legal (mcts.rs:196-200); the slot then stays exactly as it is.
+      uint32_t refused = 0;
+      uint32_t root_term = 0;                                // hold: terminal state of the root, before and after the move
+      if (RESUME && sim == 0) {
+        root_term = c4::terminal_state(rmask, rvalue);        // (any start position: the full test)
+        if (mv != C4_HOLD_MOVE_NONE) {
+          if (root_term) refused = C4_HOLD_REFUSED_TERMINAL;
+          else if (mv != C4_HOLD_MOVE_SAMPLE && (mv < 0 || mv > 6 || !((c4::legal_mask(rmask) >> mv) & 1u))) refused = C4_HOLD_REFUSED_COLUMN;
+          else if (root_block == 0) refused = C4_HOLD_REFUSED_UNSEARCHED;
+        }
+      }
+      // (A terminal START position is a finished game as it stands: c4_session_start's launch closes it with its one sample.)
+      if (!SEARCH && (HOLD ? (RESUME && sim == 0 && ((mv != C4_HOLD_MOVE_NONE && !refused) || (p.hold_fresh && root_term != 0)))
+                           : ((root_n >= p.n_iter && !(p.flags & C4_FLAG_NO_MOVES)) || term_start))) {
         const size_t rec0 = (size_t)ordinal * C4_MAX_SAMPLES_PER_GAME;
-        uint32_t rterm = term_start ? term : 0u;             // a root is terminal only as a terminal START position
+        uint32_t rterm = HOLD ? root_term : (term_start ? term : 0u);   // a root is terminal only as a terminal START position
         uint32_t retained = term_start ? 0u : p.n_iter;
         if (!rterm) {
           // root_policy (mcts.rs:396-412): child visit counts / their sum
@@ -680,20 +730,21 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
           for (int i = 0; i < 7; i++) pol[i] = (csum == 0.0f) ? (1.0f / 7.0f) : (w[i] / csum);
           // make_random_move (mcts.rs:214-222); the 7 columns' logf/expf and the 4 ChaCha columns
           // run on the game's own lanes instead of 8 redundant copies
-          const float temperature = c4::temperature_for_ply((uint32_t)__popcll(rmask));
+          const float temperature = HOLD ? mv_temp : c4::temperature_for_ply((uint32_t)__popcll(rmask));
           C4_STAMP_TRIP1(9, (uint32_t)pol[0]);
           float tp[7];
           c4::apply_temperature_group(pol, temperature, tp, sub, gbase);
           C4_STAMP_TRIP1(10, (uint32_t)tp[0]);
           const uint64_t seed = game_id * (uint64_t)(42 + n_moves);
           // the word was normally computed in an earlier, uncontended step (end of this kernel)
-          const uint32_t u32 = (!fresh && rng_for == n_moves + 1) ? rng_word : c4::rng_first_u32_group(seed, sub, gbase);
-          const int col = c4::weighted_index(tp, u32);
+          // (a hold session keeps no precomputed word: its moves come from outside, one launch each)
+          const uint32_t u32 = (!HOLD && !fresh && rng_for == n_moves + 1) ? rng_word : c4::rng_first_u32_group(seed, sub, gbase);
+          const int col = (HOLD && mv >= 0) ? (int)mv : c4::weighted_index(tp, u32);
           C4_STAMP_TRIP1(11, (uint32_t)col);
           if (col < 0) {
             err = C4_ERR_DEGENERATE_POLICY;
           } else if (!((c4::legal_mask(rmask) >> col) & 1u)) {
-            err = C4_ERR_ILLEGAL_MOVE;                                        // mcts.rs:196-200 expect()
+            if (HOLD) refused = C4_HOLD_REFUSED_SAMPLE; else err = C4_ERR_ILLEGAL_MOVE;   // mcts.rs:196-200 expect()
           } else {
             // make_move (mcts.rs:187-206): record (root position, untempered policy), re-root
             c4_sample_rec* rec = p.samples + rec0 + n_moves;
@@ -732,7 +783,7 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
           // reference keeps evaluating that root until it has n visits (self_play.rs:283-301);
           // those sims cannot change the samples (mcts.rs:271-313), so the game is closed now
           // and the skipped sims are counted.
-          c_skipped += (p.n_iter > retained) ? (p.n_iter - retained) : 0;
+          if (!HOLD) c_skipped += (p.n_iter > retained) ? (p.n_iter - retained) : 0;   // (the reference's InteractivePlay stops at a terminal root too)
           float tq_pen, tq_nopen;
           c4::terminal_value(rterm, rmask, p.c_ply_penalty, tq_pen, tq_nopen);
           // to_result (mcts.rs:271-313): sample i gets +q iff (M - i) is even
@@ -752,14 +803,32 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
           c_samples += n_moves + 1;
           finished = true;
         }
+        if (HOLD) root_term = rterm;
       }
       // Did any game of this wavefront move in this launch?  Asked here, where every game that entered the
       // trip is still in it (a wavefront's 8 games run in lock-step: one game's extra work is everybody's).
-      const bool wave_moved = SEARCH ? false : (__ballot(c_moves != 0) != 0ull);   // (a search never moves)
+      const bool wave_moved = (SEARCH || HOLD) ? false : (__ballot(c_moves != 0) != 0ull);   // (a search never moves; a hold session not in a step)
       if (err) break;
+      if (HOLD) {
+        // The hold gate (State::bg_thread_should_stop, interactive_play.rs:188-191), inside the trip loop: a root never gets a
+        // visit beyond its target.  A refused move, and a resume that finds a search under way with visits still to go, leave
+        // the slot as it is, pending leaf and all.
+        if (RESUME && sim == 0 && refused) {
+          if (sub == 0 && p.hold_results) p.hold_results[g] = (int32_t)refused;
+          untouched = true;
+        } else if (finished || root_term != 0 || root_n >= p.n_iter) {
+          if (finished && sub == 0) atomicAdd(&p.glob->games_done, 1ull);
+          park = true;
+          leaf_mask = rmask; leaf_value = rvalue; depth = 0; term = root_term;
+          pv.x = (sub == 4) ? root_ref : pv.x;
+        } else if (RESUME && sim == 0 && was_active && c_moves == 0) {
+          untouched = true;
+        }
+        if (park || untouched) break;
+      }
 
       C4_STAMP_TRIP1(12, root_n);
-      if (finished) {
+      if (!HOLD && finished) {
         // replace the finished game by the next one of the request list (keeps the batch full)
         unsigned long long next = 0;
         if (sub == 0) {
@@ -819,20 +888,32 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
 #undef C4_STAMP_TRIP1
     if (err) {
       if (sub == 0) raise_error(p, st, g, err);
+    } else if (HOLD && untouched) {
+      // nothing: the slot stays byte for byte what it was
     } else if (active) {
-      if (sub == 0) publish_leaf_model(p, g, ordinal, leaf_mask);
+      const bool waits = !(HOLD && park);   // (a parked game waits for no evaluator row)
+      if (waits && sub == 0) publish_leaf_model(p, g, ordinal, leaf_mask);
       pre_need = fresh || (rng_for != n_moves + 1);   // after a move / refill the stored word is stale
       pre_n_moves = n_moves;
       pre_game_id = game_id;
       // ---------------- leaf -> evaluator input (c4r.rs:378-392) ----------------------
-      encode_leaf<PlaneT>(p.planes, g, leaf_mask, leaf_value, sub);
+      if (waits) encode_leaf<PlaneT>(p.planes, g, leaf_mask, leaf_value, sub);
       // ---------------- the game's state goes back as one line: lane k owns dwords 4k..4k+3 ----
       line = pv;                                                    // lanes 4..7: the recorded path
       if (sub == 0) line = make_uint4((uint32_t)rmask, (uint32_t)(rmask >> 32), (uint32_t)rvalue, (uint32_t)(rvalue >> 32));
       if (sub == 1) line = make_uint4((uint32_t)leaf_mask, (uint32_t)(leaf_mask >> 32), (uint32_t)leaf_value, (uint32_t)(leaf_value >> 32));
       if (sub == 2) line = make_uint4((uint32_t)game_id, (uint32_t)(game_id >> 32), ordinal, root_n);
-      if (sub == 3) line = make_uint4(slot_state(kActive, depth, n_moves, term, fresh ? 0u : rng_for), n_blocks | (root_block << 16), root_ref, rng_word);
+      if (sub == 3) line = make_uint4(slot_state((HOLD && park) ? kParked : kActive, depth, n_moves, term, fresh ? 0u : rng_for), n_blocks | (root_block << 16), root_ref, rng_word);
       store_line = true;
+    }
+  }
+  if (HOLD) {
+    // the session's count of active slots (c4_session_hold_poll), and how far the farthest root is from its target
+    const bool now_active = untouched ? was_active : (store_line && !park);
+    if (sub == 0 && g < n_slots && now_active != was_active) atomicAdd(&p.glob->hold_active, now_active ? 1u : 0xFFFFFFFFu);
+    const uint32_t have = shfl_u32(line.w, gbase + 2);   // the root's visit count as the slot's line holds it
+    if (RESUME && sub == 0 && g < n_slots && now_active) {
+      atomicMax(&p.glob->hold_need, p.n_iter > have ? p.n_iter - have : 0u);
     }
   }
 
@@ -857,7 +938,7 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
   // The launch lasts as long as its slowest wavefront, and that is one with a MOVING game.  The
   // ChaCha12 word a game will need at its next move depends only on (game_id, moves played), so it
   // is computed here, in a step where no game of this wavefront moved, and kept in the slot.
-  if (!SEARCH && __ballot(c_moves != 0) == 0ull && pre_need) {
+  if (!SEARCH && !HOLD && __ballot(c_moves != 0) == 0ull && pre_need) {
     const uint32_t w = c4::rng_first_u32_group(pre_game_id * (uint64_t)(42 + pre_n_moves), sub, gbase);
     if (sub == 3) { line.w = w; line.x = (line.x & 0x03FFFFFFu) | ((pre_n_moves + 1u) << 26); }
   }
@@ -870,7 +951,7 @@ C4_DEV void step_body(const Params& p, const uint32_t wave_index, const uint32_t
   }
 }
 
-template <typename PlaneT, bool NOISE, bool CACHE, bool SEARCH = false>
+template <typename PlaneT, bool NOISE, bool CACHE, bool SEARCH = false, bool HOLD = false>
 __global__ __launch_bounds__(64, (NOISE || CACHE) ? 1 : C4_STEP_WAVES) void c4_step_kernel(
     // What the head of every wavefront's dependent chain needs, as leading SCALAR arguments (copies of p's fields): with
     // -mllvm -amdgpu-kernarg-preload-count (build.py) they are in SGPRs when the wavefront starts, so the state line and
@@ -899,7 +980,71 @@ __global__ __launch_bounds__(64, (NOISE || CACHE) ? 1 : C4_STEP_WAVES) void c4_s
   // `if (active)` below, i.e. behind the wait for the state line -- a second, serial memory round trip (plus the
   // scalar loads of the two pointers) at the head of every wavefront's chain (round 3, found in the ISA).
   __builtin_amdgcn_sched_barrier(0);
-  step_body<PlaneT, NOISE, CACHE, SEARCH>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, t_start, g);
+  step_body<PlaneT, NOISE, CACHE, SEARCH, HOLD>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, t_start, g);
+}
+
+// ------------------------------------------------------------------------------------------
+// Hold sessions (C4_FLAG_HOLD): the single place where a game becomes active (c4_session_start, c4_session_hold_resume).  For every
+// slot with a game, 8 lanes per game like the step: an optional move from outside, then park -- the root is terminal or has its
+// n_iter visits -- or select the next leaf from the tree as it stands, encode it and publish the state line as active.  All of it is
+// the tail of step_body (its RESUME form: gate -> select -> encode -> write-back), so the select, the path write-back and the deep
+// path are the step's own code.  c4_session_start's launch (p.hold_fresh) first puts request g on slot g (MctsGame::new_from_pos).
+// ------------------------------------------------------------------------------------------
+template <typename PlaneT>
+__global__ __launch_bounds__(64) void k_hold_resume(Params p) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t sub = lane & 7;
+  const uint32_t wave_index = blockIdx.x;
+  const uint32_t g = wave_index * 8 + (lane >> 3);
+  const uint32_t gs = g < p.n_slots ? g : 0;
+  Slot* st = p.slots + gs;
+  if (p.hold_fresh && g < p.n_slots) {
+    if (g < p.n_games) {
+      reset_slot(p, st, p.blocks + (size_t)g * p.blocks_per_slot, sub, g);
+    } else if (sub == 0) {
+      st->state = kIdle;
+      st->ordinal = 0xFFFFFFFFu;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // read back below by the other lanes of this wavefront
+  }
+  const uint4 hot = reinterpret_cast<const uint4*>(st)[sub];
+  step_body<PlaneT, false, false, false, true, true>(p, wave_index, lane, p.n_slots, st, hot, 0.0f, 0.0f, 0ull, g);
+}
+
+// c4_session_snapshot: InteractivePlay::snapshot (interactive_play.rs:57, 145-166) of every slot with a game, in ONE launch -- the
+// root position, root_policy (mcts.rs:396-412), the root's q as q_sum / (visits + 1) (mcts.rs:359-367: the arithmetic of
+// c4_session_root_stats and of a search record), the root's visit count and the slot's status.  8 lanes per slot.
+__global__ __launch_bounds__(64) void k_hold_snapshot(Params p, c4_sample_rec* dst, uint32_t* visits, uint32_t* status) {
+  const uint32_t lane = threadIdx.x & 63, sub = lane & 7;
+  const int gbase = (int)(lane & ~7u);
+  const uint32_t g = blockIdx.x * 8 + (lane >> 3);
+  const uint32_t gs = g < p.n_slots ? g : 0;
+  const Slot* st = p.slots + gs;
+  const Block* blocks = p.blocks + (size_t)gs * p.blocks_per_slot;
+  const uint32_t state = st->state, root_block = st->arena >> 16, root_ref = st->root_ref;
+  const bool game = slot_status(state) != kIdle;
+  const uint4 re = load_block_lane(blocks, game ? root_block : 0u, sub);
+  const float cnt = (game && sub < 7 && root_block != 0) ? (float)re.x : 0.0f;
+  float w[7];
+  float csum = 0.0f;
+  for (int i = 0; i < 7; i++) { w[i] = shfl_f32(cnt, gbase + i); csum = csum + w[i]; }
+  if (g >= p.n_slots) return;
+  c4_sample_rec* rec = dst + g;
+  if (!game) {
+    reinterpret_cast<uint2*>(rec)[sub] = make_uint2(0u, 0u);
+    if (sub == 7) { visits[g] = 0; status[g] = kIdle; }
+    return;
+  }
+  if (sub < 7) rec->policy[sub] = (csum == 0.0f) ? (1.0f / 7.0f) : (w[sub] / csum);
+  if (sub == 7) {
+    const Entry* re0 = &blocks[root_ref >> 3].e[root_ref & 7];
+    const float nf = (float)re0->n + 1.0f;
+    rec->game_id = st->game_id; rec->mask = st->root_mask; rec->value = st->root_value;
+    rec->q_penalty = re0->q_pen / nf; rec->q_no_penalty = re0->q_nopen / nf;
+    rec->meta = ((state >> 16) & 0xFFu) | (3u << 16);
+    visits[g] = re0->n;
+    status[g] = slot_status(state);
+  }
 }
 
 // c4_session_scatter_outputs + c4_session_step as ONE launch (callback mode, c4_session_step_gather): a game takes its evaluator
@@ -955,7 +1100,8 @@ __global__ __launch_bounds__(64, (NOISE || CACHE) ? 1 : C4_STEP_WAVES) void c4_s
 // -0.4 %: the paired driver asks for 4, everybody else gets 8.  Which wavefront steps a game changes nothing the game records.
 // (Counter rows: two wavefronts add to one row, by atomics as before.)
 // SEARCH: the step of a search session (C4_FLAG_SEARCH, see step_body); the output layers are the same code.
-template <typename PlaneT, uint32_t kGpw, bool SEARCH = false>
+// HOLD: the step of a hold session (C4_FLAG_HOLD), likewise.
+template <typename PlaneT, uint32_t kGpw, bool SEARCH = false, bool HOLD = false>
 __global__ __launch_bounds__(64 * c4ho::kHeadWaves, 1) C4_OUT_STEP_ATTR void c4_out_step_kernel(
     const uint4* __restrict__ hp, const uint4* __restrict__ hv, const uint4* __restrict__ wp, const uint4* __restrict__ wv,
     const float* __restrict__ bp, const float* __restrict__ bv, Slot* __restrict__ a_slots, uint32_t a_n_slots, uint32_t f8, uint32_t sp8, uint32_t sv8,
@@ -978,7 +1124,7 @@ __global__ __launch_bounds__(64 * c4ho::kHeadWaves, 1) C4_OUT_STEP_ATTR void c4_
   if (wave >= kStepWaves || wave_index >= p.n_waves) return;
   const float nn_logit = sh.res[b & 15][sub < 7 ? sub : 6];
   const float nn_q = sh.res[b & 15][7 + (sub & 1)];
-  step_body<PlaneT, false, false, SEARCH>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, 0ull, g);
+  step_body<PlaneT, false, false, SEARCH, HOLD>(p, wave_index, lane, a_n_slots, st, hot, nn_logit, nn_q, 0ull, g);
   C4_TL_END(3, a_slots);
 }
 
@@ -1444,6 +1590,16 @@ struct c4_session {
   uint32_t reclaim_period = 0;
   uint32_t reclaim_count = 0;
   unsigned long long reclaim_capture_id = 0;
+  // hold sessions (C4_FLAG_HOLD): staging for per-slot arrays handed over in pageable host memory (cols, temperatures, results),
+  // the snapshot's device and pinned buffers, and the active-slot probe (valid once a probe enqueued after the last resume landed)
+  int32_t* hold_cols_dev = nullptr;
+  float* hold_temps_dev = nullptr;
+  int32_t* hold_results_dev = nullptr;
+  unsigned char* snap_dev = nullptr;
+  unsigned char* snap_host = nullptr;
+  uint32_t hold_epoch = 0, probe_epoch = 0;
+  bool hold_probe_valid = false;
+  uint32_t hold_probe_active = 0, hold_probe_need = 0;
 };
 
 C4_TL_SETTER(c4_debug_timeline_session)
@@ -1546,9 +1702,10 @@ static uint64_t reclaim_half_min(uint32_t n_iter, uint32_t period, uint32_t max_
 }
 static bool reclaim_mode(const c4_config* cfg) {
   return (cfg->flags & C4_FLAG_RECLAIM) != 0 ||
-         (cfg->blocks_per_slot == 0 && cfg->n_mcts_iterations > kReclaimAuto && !(cfg->flags & (C4_FLAG_NO_MOVES | C4_FLAG_NO_RECLAIM | C4_FLAG_SEARCH)));
+         (cfg->blocks_per_slot == 0 && cfg->n_mcts_iterations > kReclaimAuto && !(cfg->flags & (C4_FLAG_NO_MOVES | C4_FLAG_NO_RECLAIM | C4_FLAG_SEARCH | C4_FLAG_HOLD)));
 }
 static bool search_mode(const c4_session* s) { return (s->cfg.flags & C4_FLAG_SEARCH) != 0; }
+static bool hold_mode(const c4_session* s) { return (s->cfg.flags & C4_FLAG_HOLD) != 0; }
 
 // Called behind every step launch of a reclaimed session: every `period`-th launch is followed by k_arena_reclaim on the same
 // stream.  Launches are counted per capture while the stream is being captured into a HIP graph (the count restarts with the
@@ -1663,6 +1820,15 @@ int c4_session_create(const c4_config* cfg, c4_session** out) {
     if (cfg->flags & C4_FLAG_RECLAIM) return fail(C4_ERR_BAD_ARG, "C4_FLAG_SEARCH: a search never moves, so its arena (n_mcts_iterations + 8 blocks) has nothing to reclaim (C4_FLAG_RECLAIM)");
     if (cfg->n_mcts_iterations == 0) return fail(C4_ERR_BAD_ARG, "C4_FLAG_SEARCH needs n_mcts_iterations >= 1");
   }
+  // A hold session (C4_FLAG_HOLD) moves when it is told to and searches up to a target: a step-kernel instantiation of its own, like
+  // a search session's, with no noise, cache, reclaim or never-moving form; its never-reclaimed arena holds a root's n new
+  // simulations for each of a game's 42 roots at most.
+  if (cfg->flags & C4_FLAG_HOLD) {
+    if (cfg->flags & C4_FLAG_SEARCH) return fail(C4_ERR_BAD_ARG, "C4_FLAG_HOLD and C4_FLAG_SEARCH exclude each other: a search hands its slot on after one record, a held game keeps it");
+    if (cfg->flags & C4_FLAG_NO_MOVES) return fail(C4_ERR_BAD_ARG, "C4_FLAG_HOLD and C4_FLAG_NO_MOVES exclude each other: a held game parks at its target and moves when c4_session_hold_resume says so");
+    if (cfg->flags & C4_FLAG_RECLAIM) return fail(C4_ERR_BAD_ARG, "C4_FLAG_HOLD: a held game's arena is never reclaimed (C4_FLAG_RECLAIM): the subtree under a move is kept in place");
+    if (cfg->n_mcts_iterations == 0) return fail(C4_ERR_BAD_ARG, "C4_FLAG_HOLD needs n_mcts_iterations >= 1 (the largest target c4_session_set_iterations may ask for)");
+  }
   if (reclaim_mode(cfg)) {
     const uint32_t period = cfg->reclaim_period ? cfg->reclaim_period : kReclaimPeriod;
     const uint64_t need = reclaim_half_min(cfg->n_mcts_iterations, period, 2);
@@ -1706,6 +1872,8 @@ int c4_session_destroy(c4_session* s) {
   if (s->total_host) (void)hipHostFree(s->total_host);
   (void)hipFree(s->uniq_tab); (void)hipFree(s->uniq_cell); (void)hipFree(s->uniq_row); (void)hipFree(s->uniq_count);
   (void)hipFree(s->reqs_dev); (void)hipFree(s->start_mask_dev); (void)hipFree(s->start_value_dev);
+  (void)hipFree(s->hold_cols_dev); (void)hipFree(s->hold_temps_dev); (void)hipFree(s->hold_results_dev); (void)hipFree(s->snap_dev);
+  if (s->snap_host) (void)hipHostFree(s->snap_host);
   if (s->probe_host) (void)hipHostFree(s->probe_host);
   if (s->probe_event) (void)hipEventDestroy(s->probe_event);
   delete s;
@@ -1731,6 +1899,9 @@ int c4_session_set_games(c4_session* s, const c4_game_metadata* reqs, uint64_t n
   if (!s || (!reqs && n_games)) return fail(C4_ERR_BAD_ARG, "null argument");
   if ((start_masks == nullptr) != (start_values == nullptr)) return fail(C4_ERR_BAD_ARG, "start_masks and start_values go together");
   if (n_games >= (1ull << 32) - 1) return fail(C4_ERR_BAD_ARG, "too many games for one session");
+  if (hold_mode(s) && n_games > s->cfg.n_slots)
+    return fail(C4_ERR_BAD_ARG, "c4_session_set_games: a hold session (C4_FLAG_HOLD) keeps request i on slot i for good: " + std::to_string(n_games) +
+                                    " games do not fit " + std::to_string(s->cfg.n_slots) + " slots");
   C4_ON_DEVICE(s->cfg.device);
   HIP_TRY(hipStreamSynchronize(s->stream));
   (void)hipFree(s->reqs_dev); (void)hipFree(s->start_mask_dev); (void)hipFree(s->start_value_dev);
@@ -1771,6 +1942,7 @@ int c4_session_set_games(c4_session* s, const c4_game_metadata* reqs, uint64_t n
   s->reclaim_count = 0; s->reclaim_capture_id = 0;
   HIP_TRY(hipMemset(s->p.reclaim_ctr, 0, 2 * sizeof(unsigned long long)));
   s->probe_pending = false; s->probe_done = 0; s->probe_error = 0;
+  s->hold_epoch++; s->hold_probe_valid = false;
   return C4_OK;
 }
 
@@ -1811,6 +1983,7 @@ int c4_session_set_dirichlet(c4_session* s, float alpha, float epsilon) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (!(epsilon >= 0.0f && epsilon <= 1.0f) || (epsilon > 0.0f && !(alpha > 0.0f))) return fail(C4_ERR_BAD_ARG, "need 0 <= epsilon <= 1 and alpha > 0");
   if (epsilon > 0.0f && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_dirichlet: a search session (C4_FLAG_SEARCH) has no Dirichlet-noise step kernel");
+  if (epsilon > 0.0f && hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_dirichlet: a hold session (C4_FLAG_HOLD) has no Dirichlet-noise step kernel");
   s->p.dir_alpha = alpha;
   s->p.dir_eps = epsilon;
   return C4_OK;
@@ -1819,6 +1992,7 @@ int c4_session_set_dirichlet(c4_session* s, float alpha, float epsilon) {
 int c4_session_bind_leaf_models(c4_session* s, uint64_t* leaf_models_dev) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (leaf_models_dev && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_bind_leaf_models: a search session (C4_FLAG_SEARCH) has ONE evaluator");
+  if (leaf_models_dev && hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_bind_leaf_models: a hold session (C4_FLAG_HOLD) has ONE evaluator (a match is two sessions exchanging moves)");
   if (leaf_models_dev && s->p.cache) return fail(C4_ERR_BAD_ARG, "the evaluation cache holds ONE evaluator's outputs: not with multi-model games");
   s->p.leaf_models = leaf_models_dev;
   return C4_OK;
@@ -1829,6 +2003,7 @@ int c4_session_set_eval_cache(c4_session* s, uint64_t n_entries, uint32_t max_si
   if (n_entries && s->p.leaf_models) return fail(C4_ERR_BAD_ARG, "the evaluation cache holds ONE evaluator's outputs: not with multi-model games");
   if (n_entries > (1ull << 31)) return fail(C4_ERR_BAD_ARG, "at most 2^31 cache entries");
   if (n_entries && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_eval_cache: a search session (C4_FLAG_SEARCH) has no evaluation-cache step kernel");
+  if (n_entries && hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_eval_cache: a hold session (C4_FLAG_HOLD) has no evaluation-cache step kernel");
   C4_ON_DEVICE(s->cfg.device);
   HIP_TRY(hipStreamSynchronize(s->stream));
   (void)hipFree(s->p.cache);
@@ -1854,10 +2029,26 @@ int c4_session_set_eval_cache(c4_session* s, uint64_t n_entries, uint32_t max_si
   return C4_OK;
 }
 
+// k_hold_resume on the session's stream: the arrays are device views (or null); fresh = c4_session_start's launch
+static int hold_launch_resume(c4_session* s, const int32_t* cols, const float* temps, int32_t* results, bool fresh) {
+  Params q = s->p;
+  q.seq = 0;
+  q.hold_cols = cols; q.hold_temps = temps; q.hold_results = results; q.hold_fresh = fresh ? 1u : 0u;
+  s->hold_epoch++;   // what a probe enqueued before this point saw is history
+  s->hold_probe_valid = false;
+  HIP_TRY(hipMemsetAsync(&s->p.glob->hold_need, 0, sizeof(uint32_t), s->stream));
+  if (fresh) HIP_TRY(hipMemsetAsync(&s->p.glob->hold_active, 0, sizeof(uint32_t), s->stream));   // every slot is counted anew
+  if (s->cfg.planes_dtype == 0) hipLaunchKernelGGL(k_hold_resume<float>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, q);
+  else hipLaunchKernelGGL(k_hold_resume<uint16_t>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, q);
+  HIP_TRY(hipGetLastError());
+  return C4_OK;
+}
+
 int c4_session_start(c4_session* s) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (!s->bound || !s->have_games) return fail(C4_ERR_NOT_BOUND, "bind_io and set_games must precede start");
   C4_ON_DEVICE(s->cfg.device);
+  if (hold_mode(s)) return hold_launch_resume(s, nullptr, nullptr, nullptr, true);   // reset_slot + the one kernel that makes a game active
   if (s->cfg.planes_dtype == 0)
     hipLaunchKernelGGL(c4_start_kernel<float>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, s->p);
   else
@@ -1906,6 +2097,8 @@ static int launch_step(c4_session* s, const uint32_t* inverse, const float* answ
   } while (0)
   if (search_mode(s)) {   // no noise, cache or gather form (refused where they are asked for)
     if (f32) launch(c4_step_kernel<float, false, false, true>); else launch(c4_step_kernel<uint16_t, false, false, true>);
+  } else if (hold_mode(s)) {   // likewise
+    if (f32) launch(c4_step_kernel<float, false, false, false, true>); else launch(c4_step_kernel<uint16_t, false, false, false, true>);
   } else if (inverse) C4_LAUNCH_STEP(c4_step_gather_kernel, launch_gather); else C4_LAUNCH_STEP(c4_step_kernel, launch);
 #undef C4_LAUNCH_STEP
   HIP_TRY(hipGetLastError());
@@ -1917,6 +2110,7 @@ int c4_session_step(c4_session* s) { return launch_step(s, nullptr, nullptr, 0);
 int c4_session_step_gather(c4_session* s, const uint32_t* inverse_dev, const float* answers, uint32_t n_unique) {
   if (!s || !inverse_dev || (!answers && n_unique)) return fail(C4_ERR_BAD_ARG, "null argument");
   if (search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_step_gather: a search session (C4_FLAG_SEARCH) takes a device evaluator, not the callback mode's batches");
+  if (hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_step_gather: a hold session (C4_FLAG_HOLD) takes a device evaluator, not the callback mode's batches");
   if (!s->bound) return fail(C4_ERR_NOT_BOUND, "c4_session_step_gather: bind_io first");
   void *inv = nullptr, *ans = nullptr;
   {
@@ -1951,6 +2145,10 @@ int c4_session_step_head_out(c4_session* s, const void* hidden_policy_dev, const
     if (s->cfg.planes_dtype == 0)
       return fail(C4_ERR_BAD_ARG, "c4_session_step_head_out: a search session's fused launch is built for bf16 planes (planes_dtype 1): call c4_head_out_bf16 and c4_session_step");
     if (s->out_step_gpw == 4) launch(c4_out_step_kernel<uint16_t, 4, true>); else launch(c4_out_step_kernel<uint16_t, 8, true>);
+  } else if (hold_mode(s)) {
+    if (s->cfg.planes_dtype == 0)
+      return fail(C4_ERR_BAD_ARG, "c4_session_step_head_out: a hold session's fused launch is built for bf16 planes (planes_dtype 1): call c4_head_out_bf16 and c4_session_step");
+    if (s->out_step_gpw == 4) launch(c4_out_step_kernel<uint16_t, 4, false, true>); else launch(c4_out_step_kernel<uint16_t, 8, false, true>);
   } else if (s->out_step_gpw == 4) {
     if (s->cfg.planes_dtype == 0) launch(c4_out_step_kernel<float, 4>); else launch(c4_out_step_kernel<uint16_t, 4>);
   } else {
@@ -2024,12 +2222,18 @@ int c4_session_poll(c4_session* s, uint64_t* games_done, uint32_t* error) {
     s->probe_done = s->probe_host->games_done;
     s->probe_started = s->probe_host->queue_head < s->n_games ? s->probe_host->queue_head : s->n_games;
     s->probe_error = s->probe_host->error;
+    if (s->probe_epoch == s->hold_epoch) {   // (hold sessions) enqueued behind the last c4_session_hold_resume
+      s->hold_probe_valid = true;
+      s->hold_probe_active = s->probe_host->hold_active;
+      s->hold_probe_need = s->probe_host->hold_need;
+    }
     s->probe_pending = false;
   }
   if (!s->probe_pending) {
     HIP_TRY(hipMemcpyAsync(s->probe_host, s->p.glob, sizeof(Globals), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipEventRecord(s->probe_event, s->stream));
     s->probe_pending = true;
+    s->probe_epoch = s->hold_epoch;
   }
   if (games_done) *games_done = s->probe_done;
   if (error) *error = s->probe_error;
@@ -2045,6 +2249,7 @@ int c4_session_progress(c4_session* s, uint64_t* games_done, uint64_t* games_sta
 int c4_session_compact(c4_session* s, uint32_t multiple, uint32_t* n_active, uint32_t* n_slots_now) {
   if (!s || !s->bound || !s->have_games) return fail(C4_ERR_BAD_ARG, "compact needs a bound session with games");
   if (s->p.leaf_models) return fail(C4_ERR_BAD_ARG, "compaction does not move the per-slot model ids of multi-model sessions");
+  if (hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_compact: a hold session (C4_FLAG_HOLD) keeps request i on slot i: its per-slot arrays are indexed by it");
   if (multiple == 0 || multiple % 8) return fail(C4_ERR_BAD_ARG, "multiple must be a positive multiple of 8");
   C4_ON_DEVICE(s->cfg.device);
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -2224,6 +2429,7 @@ static int device_view(const void* ptr, int device, const char* what, void** out
 int c4_session_unique_leaves(c4_session* s, uint32_t* inverse_dev, float* rows_out, uint64_t* models_out, uint32_t* n_unique_out) {
   if (!s || !inverse_dev || !rows_out || !n_unique_out) return fail(C4_ERR_BAD_ARG, "null argument");
   if (search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: a search session (C4_FLAG_SEARCH) takes a device evaluator, not the callback mode's batches");
+  if (hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: a hold session (C4_FLAG_HOLD) takes a device evaluator, not the callback mode's batches");
   if (!s->bound || !s->have_games) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: bind_io and set_games first");
   C4_ON_DEVICE(s->cfg.device);
   const uint32_t n = s->cfg.n_slots;
@@ -2288,6 +2494,85 @@ int c4_session_leaves(c4_session* s, uint64_t* masks_host, uint64_t* values_host
     if (status_host) status_host[g] = h[g].state & 0xFFu;
     if (ordinals_host) ordinals_host[g] = h[g].ordinal;
   }
+  return C4_OK;
+}
+
+// ---- hold sessions (C4_FLAG_HOLD): target, moves from outside, snapshot, probe ----
+int c4_session_set_iterations(c4_session* s, uint32_t n_mcts_iterations) {
+  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
+  if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_iterations: not a hold session (C4_FLAG_HOLD); a session of games or searches keeps the n_mcts_iterations it was created with");
+  if (n_mcts_iterations < 1 || n_mcts_iterations > s->cfg.n_mcts_iterations)
+    return fail(C4_ERR_BAD_ARG, "c4_session_set_iterations: the target must be between 1 and the n_mcts_iterations the session was created with (" +
+                                    std::to_string(s->cfg.n_mcts_iterations) + "), which sizes its tree arena and its table of logarithms");
+  s->p.n_iter = n_mcts_iterations;   // a kernel argument of every later launch: stream-ordered by construction
+  return C4_OK;
+}
+
+// One per-slot array of c4_session_hold_resume as the kernel may use it: device memory and pinned host memory through
+// device_view; pageable host memory (what HIP does not know) through the session's staging buffer `stage` (copied in now when
+// `copy_in`).  *staged tells the caller which.
+static int hold_array(c4_session* s, const void* ptr, void** stage, bool copy_in, const char* what, void** out, bool* staged) {
+  const size_t bytes = (size_t)s->cfg.n_slots * 4;
+  *staged = false;
+  hipPointerAttribute_t attr{};
+  const hipError_t e = hipPointerGetAttributes(&attr, ptr);
+  if (e == hipSuccess && attr.type != hipMemoryTypeUnregistered) return device_view(ptr, s->cfg.device, what, out);
+  if (e != hipSuccess) (void)hipGetLastError();
+  if (!*stage) HIP_TRY(hipMalloc(stage, bytes));
+  if (copy_in) HIP_TRY(hipMemcpyAsync(*stage, ptr, bytes, hipMemcpyHostToDevice, s->stream));
+  *out = *stage;
+  *staged = true;
+  return C4_OK;
+}
+
+int c4_session_hold_resume(c4_session* s, const int32_t* cols, const float* temperatures, int32_t* results) {
+  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
+  if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_hold_resume: not a hold session (C4_FLAG_HOLD)");
+  if (!s->bound || !s->have_games) return fail(C4_ERR_NOT_BOUND, "bind_io and set_games must precede c4_session_hold_resume");
+  if (!cols && (temperatures || results)) return fail(C4_ERR_BAD_ARG, "c4_session_hold_resume: temperatures and results go with cols");
+  C4_ON_DEVICE(s->cfg.device);
+  void *c = nullptr, *t = nullptr, *r = nullptr;
+  bool sc = false, st = false, sr = false;
+  if (cols) if (int rc = hold_array(s, cols, (void**)&s->hold_cols_dev, true, "c4_session_hold_resume: cols", &c, &sc)) return rc;
+  if (temperatures) if (int rc = hold_array(s, temperatures, (void**)&s->hold_temps_dev, true, "c4_session_hold_resume: temperatures", &t, &st)) return rc;
+  if (results) if (int rc = hold_array(s, results, (void**)&s->hold_results_dev, false, "c4_session_hold_resume: results", &r, &sr)) return rc;
+  if (int rc = hold_launch_resume(s, (const int32_t*)c, (const float*)t, (int32_t*)r, false)) return rc;
+  if (sr) HIP_TRY(hipMemcpyAsync(results, r, (size_t)s->cfg.n_slots * 4, hipMemcpyDeviceToHost, s->stream));
+  if (sc || st || sr) HIP_TRY(hipStreamSynchronize(s->stream));   // pageable host memory: the caller's arrays are done with when the call returns
+  return C4_OK;
+}
+
+int c4_session_snapshot(c4_session* s, c4_sample_rec* dst_host, uint32_t* visits_host, uint32_t* status_host, uint64_t cap) {
+  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
+  if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_snapshot: not a hold session (C4_FLAG_HOLD)");
+  if (!s->have_games) return fail(C4_ERR_NOT_BOUND, "set_games must precede c4_session_snapshot");
+  const size_t n = s->cfg.n_slots;
+  if (cap < n) return fail(C4_ERR_BAD_ARG, "c4_session_snapshot: the arrays hold one entry per slot (" + std::to_string(n) + ")");
+  C4_ON_DEVICE(s->cfg.device);
+  const size_t bytes = n * (sizeof(c4_sample_rec) + 8);   // [n] records, [n] visit counts, [n] status words
+  if (!s->snap_dev) {
+    HIP_TRY(hipMalloc(&s->snap_dev, bytes));
+    HIP_TRY(hipHostMalloc(&s->snap_host, bytes));
+  }
+  c4_sample_rec* recs = (c4_sample_rec*)s->snap_dev;
+  uint32_t* visits = (uint32_t*)(s->snap_dev + n * sizeof(c4_sample_rec));
+  hipLaunchKernelGGL(k_hold_snapshot, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, s->stream, s->p, recs, visits, visits + n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(s->snap_host, s->snap_dev, bytes, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (dst_host) memcpy(dst_host, s->snap_host, n * sizeof(c4_sample_rec));
+  if (visits_host) memcpy(visits_host, s->snap_host + n * sizeof(c4_sample_rec), n * 4);
+  if (status_host) memcpy(status_host, s->snap_host + n * sizeof(c4_sample_rec) + n * 4, n * 4);
+  return C4_OK;
+}
+
+int c4_session_hold_poll(c4_session* s, uint32_t* n_active, uint32_t* max_need, uint32_t* error) {
+  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
+  if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_hold_poll: not a hold session (C4_FLAG_HOLD)");
+  const int rc = c4_session_poll(s, nullptr, error);
+  if (rc != C4_OK) return rc;
+  if (n_active) *n_active = s->hold_probe_valid ? s->hold_probe_active : C4_HOLD_POLL_UNKNOWN;
+  if (max_need) *max_need = s->hold_probe_valid ? s->hold_probe_need : C4_HOLD_POLL_UNKNOWN;
   return C4_OK;
 }
 

@@ -59,11 +59,15 @@ class DeviceSession:
     def __init__(self, n_slots: int, n_mcts_iterations: int, c_exploration: float, c_ply_penalty: float,
                  device: Optional[torch.device] = None, planes_dtype: torch.dtype = torch.float32,
                  blocks_per_slot: int = 0, no_moves: bool = False, one_sim_per_step: bool = False,
-                 reclaim: Optional[bool] = None, reclaim_period: int = 0, search: bool = False):
+                 reclaim: Optional[bool] = None, reclaim_period: int = 0, search: bool = False, hold: bool = False):
         """search: True = every request is ONE search of its start position (set_games(reqs, start_positions)), not a game:
         n_mcts_iterations simulations, then one record -- the root policy and the root's two q values, meta = 2 << 16 -- and the slot
         takes the next request (C4_FLAG_SEARCH; MctsGame::new_from_pos + run_mcts, mcts.rs:48-56, 469-485).  Device evaluators only;
         no Dirichlet noise, evaluation cache or reclaimed arena.  compact / capture_steps / run / run_sessions / capture_pair as for games.
+        hold: True = every request is ONE persistent game on its own slot (C4_FLAG_HOLD; the reference's InteractivePlay,
+        interactive_play.rs): searched up to a target (n_mcts_iterations is the largest one, set_iterations changes it), parked there,
+        moved from outside (hold_resume) with the subtree under the move kept; c4a0_amd.engine.Engine drives it.  Device evaluators
+        only; no noise, cache, reclaimed arena, compact or run().
         reclaim: True = the tree arena is reclaimed while games are played (C4_FLAG_RECLAIM: the live subtree is copied into the
         arena's other half when one runs short, as the reference frees dead subtrees at every move, mcts.rs:187-206); None = the
         library decides (on above 1 000 iterations per move with the default sizing); False with more than 1 523 iterations needs
@@ -83,8 +87,9 @@ class DeviceSession:
                      float(c_ply_penalty), 0 if planes_dtype == torch.float32 else 1,
                      (_lib.FLAG_NO_MOVES if no_moves else 0) | (_lib.FLAG_ONE_SIM_PER_STEP if one_sim_per_step else 0) |
                      (_lib.FLAG_RECLAIM if reclaim else (_lib.FLAG_NO_RECLAIM if reclaim is False else 0)) |
-                     (_lib.FLAG_SEARCH if search else 0), dev_index, int(reclaim_period))
+                     (_lib.FLAG_SEARCH if search else 0) | (_lib.FLAG_HOLD if hold else 0), dev_index, int(reclaim_period))
         self.search = bool(search)
+        self.hold = bool(hold)
         h = C.c_void_p()
         check(self.L.c4_session_create(C.byref(cfg), C.byref(h)))
         self._h = h
@@ -188,7 +193,7 @@ class DeviceSession:
         capture), the heads' output layers run inside the step's launch (c4_session_step_head_out: one launch fewer on the
         round's chain, same bits); otherwise evaluate() then step()."""
         if (self.fuse_output_step and not self._timing and not self._extensions and getattr(self, "leaf_models", None) is None
-                and getattr(evaluator, "fused_step_ok", False) and not (self.search and self.planes.dtype != torch.bfloat16)):   # (a search's fused launch: bf16 planes)
+                and getattr(evaluator, "fused_step_ok", False) and not ((self.search or self.hold) and self.planes.dtype != torch.bfloat16)):   # (a search's / a hold session's fused launch: bf16 planes)
             r = self.rows
             p, v = evaluator.forward_hidden(self.planes if r == self.n_slots else self.planes[:r])
             wp, wv, bp, bv = evaluator.head_out_operands()
@@ -284,6 +289,35 @@ class DeviceSession:
         if n.value:
             check(self.L.c4_session_pack_samples(self._h, C.c_void_p(out.data_ptr()), n.value, C.byref(n)))
         return out[: n.value]
+
+    # ---------------------------------------------------------------- hold sessions (C4_FLAG_HOLD)
+    def set_iterations(self, n: int):
+        """The target every root is searched up to (absolute; at most the n_mcts_iterations the session was created with).  Graphs
+        captured earlier carry the old one."""
+        check(self.L.c4_session_set_iterations(self._h, int(n)))
+
+    def hold_resume(self, cols: Optional[torch.Tensor] = None, temperatures: Optional[torch.Tensor] = None,
+                    results: Optional[torch.Tensor] = None):
+        """c4_session_hold_resume: per slot an optional move (int32[n_slots]: -1 none, 0..6 a column, -2 sampled at float32
+        temperatures[slot]), then park or select the next leaf; results int32[n_slots] receives the per-slot codes
+        (c4a0_amd._lib.HOLD_*).  All three are device tensors that stay untouched until the stream has passed the launch.  Asynchronous."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self.L.c4_session_hold_resume(self._h, ptr(cols), ptr(temperatures), ptr(results)))
+
+    def snapshot(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """c4_session_snapshot: (records SAMPLE_DTYPE[n_slots], root visit counts uint32[n_slots], slot status uint32[n_slots])."""
+        recs = np.zeros(self.n_slots, dtype=SAMPLE_DTYPE)
+        visits, status = np.zeros(self.n_slots, dtype=np.uint32), np.zeros(self.n_slots, dtype=np.uint32)
+        check(self.L.c4_session_snapshot(self._h, recs.ctypes.data, visits.ctypes.data, status.ctypes.data, self.n_slots))
+        return recs, visits, status
+
+    def hold_poll(self) -> Tuple[Optional[int], Optional[int], int]:
+        """c4_session_hold_poll: (active slots, largest target - visits at the last resume, error); the first two are None until a
+        probe enqueued after the last resume has landed."""
+        act, need, err = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(self.L.c4_session_hold_poll(self._h, C.byref(act), C.byref(need), C.byref(err)))
+        known = act.value != _lib.HOLD_POLL_UNKNOWN
+        return (act.value if known else None), (need.value if known else None), err.value
 
     def root_stats(self, slot: int = 0):
         pol = (C.c_float * 7)()

@@ -24,10 +24,10 @@ extern "C" {
 #endif
 
 /* Version of THIS interface: bumped whenever a signature or a struct layout below changes (version 3 added `config` in the
- * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED, version 11 the f32 evaluator c4_conv_tower_f32 / c4_linear_f32 / c4_head_out_f32, version 12 C4_FLAG_SEARCH / c4_search_positions_bf16).  A consumer compiled against this header checks it once at start-up --
+ * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED, version 11 the f32 evaluator c4_conv_tower_f32 / c4_linear_f32 / c4_head_out_f32, version 12 C4_FLAG_SEARCH / c4_search_positions_bf16, version 13 C4_FLAG_HOLD / c4_session_set_iterations / c4_session_hold_resume / c4_session_snapshot / c4_session_hold_poll).  A consumer compiled against this header checks it once at start-up --
  * `if (c4_abi_version() != C4_ABI_VERSION) refuse` -- because the dynamic linker compares names, not signatures
  * (tests/abi_consumer*.c and c4a0_amd/_lib.py do).  No reference counterpart: the reference's boundary is PyO3. */
-#define C4_ABI_VERSION 12
+#define C4_ABI_VERSION 13
 
 #define C4_N_COLS 7          /* rust/src/c4r.rs:45, lib.rs:28 */
 #define C4_N_ROWS 6          /* rust/src/c4r.rs:44, lib.rs:29 */
@@ -57,7 +57,7 @@ typedef struct {
 } c4_game_metadata;
 
 /* One training sample (types.rs:103-110 Sample + the game it belongs to), 64 bytes.
- * meta = sample index within the game (low 16 bits) | flags << 16 (bit 0: terminal sample; bit 1: search record -- the one
+ * meta = sample index within the game (low 16 bits) | flags << 16 (bits 0 and 1 both: a c4_session_snapshot record, index = moves made; bit 0: terminal sample; bit 1: search record -- the one
  * record of a C4_FLAG_SEARCH request: policy = the root policy after n_mcts_iterations simulations, q_penalty / q_no_penalty = the
  * root's q values, mcts.rs:359-367, 396-412 -- not a training sample of a game). */
 typedef struct {
@@ -77,7 +77,7 @@ typedef struct {
                                  0 = automatic: up to n_mcts_iterations = 1000 the worst case of a never-reclaimed arena,
                                  43*n_mcts_iterations+8; beyond that (and up to 32 200) a RECLAIMED arena of two halves of
                                  2.5*n_mcts_iterations+554 blocks each (see C4_FLAG_RECLAIM); a search session (C4_FLAG_SEARCH):
-                                 n_mcts_iterations+8 */
+                                 n_mcts_iterations+8; a hold session (C4_FLAG_HOLD): 43*n_mcts_iterations+8, never reclaimed */
   uint32_t n_mcts_iterations; /* self_play.rs:43 */
   float c_exploration;        /* self_play.rs:44 (f32, as pybridge.rs:26) */
   float c_ply_penalty;        /* self_play.rs:45 */
@@ -119,6 +119,46 @@ typedef struct {
                                  C4_FLAG_RECLAIM or n_mcts_iterations == 0, and c4_session_set_dirichlet (epsilon > 0),
                                  c4_session_set_eval_cache (n > 0), c4_session_bind_leaf_models, c4_session_step_gather and
                                  c4_session_unique_leaves return C4_ERR_BAD_ARG on such a session. */
+
+#define C4_FLAG_HOLD 32u      /* GPU-resident interactive play: every request is ONE persistent game whose tree lives on across moves that come
+                                 from outside -- the reference's InteractivePlay around one MctsGame (interactive_play.rs; what run_tui sits on).
+                                 Request i lives on slot i for the session's whole life (c4_session_set_games: n_games <= n_slots, else
+                                 C4_ERR_BAD_ARG; any start position, MctsGame::new_from_pos); no slot is ever refilled.
+                                 Target: the session's n_mcts_iterations is InteractivePlay.max_mcts_iterations, an ABSOLUTE target for the
+                                 root's visit count, changed by c4_session_set_iterations (at most the value the session was created with).
+                                 After expand + backup a game whose root has that many visits is PARKED (State::bg_thread_should_stop,
+                                 interactive_play.rs:188-191): slot status C4_HOLD_PARKED (c4_session_leaves; not idle, not active, not a
+                                 c4_status), no leaf selected, no planes written, no move, no record; every later step skips it.  The gate sits
+                                 inside the step's loop of (at most two) simulations, so a root never gets more visits than max(target, the
+                                 visits it had when the target was set).  A game whose root is TERMINAL is never searched: it is parked from the
+                                 start, or from the move that made its root terminal -- unlike C4_FLAG_SEARCH, which searches such a root n times.
+                                 Becoming active: c4_session_start and c4_session_hold_resume, one kernel, which per slot applies the move asked
+                                 for, parks, or selects the next leaf from the tree as it stands and writes it to planes_dev.
+                                 Records: an accepted move writes what a self-play move writes (root position, untempered root policy, meta =
+                                 moves made) into the game's row of the sample store, re-roots on the child KEEPING its subtree (mcts.rs:187-206)
+                                 and, when the new root is terminal, completes the game's records as a finished self-play game's (to_result's q
+                                 signs, the uniform terminal sample, sample count; counted in games_done): c4_session_sample_counts /
+                                 _drain_samples / _pack_samples deliver finished games only, unchanged.  ref_skipped_sims stays 0.
+                                 Arena: 43 n + 8 blocks per slot by default, n the creation-time n_mcts_iterations (a root gets at most n new
+                                 simulations, a game has at most 42 roots), never reclaimed -- above n = 1 523 pass blocks_per_slot;
+                                 C4_ERR_ARENA_OVERFLOW stays the per-slot outcome of exhaustion.
+                                 A step-kernel instantiation of its own: refused together with C4_FLAG_SEARCH, C4_FLAG_NO_MOVES, C4_FLAG_RECLAIM or
+                                 n_mcts_iterations == 0, and c4_session_set_dirichlet (epsilon > 0), c4_session_set_eval_cache (n > 0),
+                                 c4_session_bind_leaf_models, c4_session_compact, c4_session_step_gather and c4_session_unique_leaves return
+                                 C4_ERR_BAD_ARG on such a session (one evaluator, one slot per game for good, device evaluators only).
+                                 c4_session_step_head_out: bf16 planes.  Not part of c4_play_games_bf16. */
+#define C4_HOLD_PARKED 64u    /* slot status of a parked game (c4_session_leaves, c4_session_snapshot) */
+/* c4_session_hold_resume: a slot's move ... */
+#define C4_HOLD_MOVE_NONE (-1)   /* none */
+#define C4_HOLD_MOVE_SAMPLE (-2) /* make_random_move(temperatures[slot]) (mcts.rs:214-222); 0..6 = that column (mcts.rs:187-206) */
+/* ... and its result */
+#define C4_HOLD_OK 0                  /* accepted, or none asked */
+#define C4_HOLD_REFUSED_TERMINAL 1    /* the root is terminal (interactive_play.rs:171, 180 return false) */
+#define C4_HOLD_REFUSED_COLUMN 2      /* the column is outside 0..6 or full (interactive_play.rs:171) */
+#define C4_HOLD_REFUSED_UNSEARCHED 3  /* the root has no children yet: not one simulation since it became the root (the reference panics, mcts.rs:196) */
+#define C4_HOLD_REFUSED_SAMPLE 4      /* the sampled column is not legal (mcts.rs:196-200 panics; only while the root's children have no visits) */
+#define C4_HOLD_NO_GAME 5             /* the slot holds no live game: never given one, or ended by a device error */
+#define C4_HOLD_POLL_UNKNOWN 0xFFFFFFFFu /* c4_session_hold_poll: no probe enqueued since the last resume has landed yet */
 
 /* Device-side counters (the reference's progress bars, self_play.rs:352-381, plus the
  * roofline numerators of SURVEY 8d).  Sums over all games since set_games. */
@@ -449,8 +489,39 @@ int c4_session_scatter_outputs(c4_session* s, const uint32_t* inverse_dev, const
  * updated: callers that watch them keep the two entry points.  Every configuration of the session (noise, cache, timing). */
 int c4_session_step_gather(c4_session* s, const uint32_t* inverse_dev, const float* answers, uint32_t n_unique);
 
+/* ---- hold sessions (C4_FLAG_HOLD, ABI 13): InteractivePlay's operations for every slot at once ---- */
+/* InteractivePlay::increase_mcts_iters (interactive_play.rs:63-67) as an absolute target: 1 <= n <= the n_mcts_iterations the session
+ * was created with (which sizes the arena and the table of logarithms), else C4_ERR_BAD_ARG.  Takes effect with the next launch on
+ * the session's stream (stream-ordered); parked games stay parked until c4_session_hold_resume.  HIP graphs captured earlier carry
+ * the old target, as after c4_session_compact: re-capture. */
+int c4_session_set_iterations(c4_session* s, uint32_t n_mcts_iterations);
+/* InteractivePlay::make_move / make_random_move (interactive_play.rs:70-85, 169-185) + ensure_bg_thread for every slot, ONE launch on
+ * the session's stream: per slot the move cols[slot] (C4_HOLD_MOVE_NONE, a column 0..6, or C4_HOLD_MOVE_SAMPLE: sampled from
+ * apply_temperature(root policy, temperatures[slot]) with seed game_id * (42 + moves made), mcts.rs:214-222), then: park if the root
+ * is terminal or has its target's visits, else select the next leaf from the tree as it stands, write it to planes_dev and make the
+ * slot active.  A move that arrives while the slot is active drops the pending leaf and selects a new one, as make_move reselects
+ * (mcts.rs:205).  A REFUSED move (results[slot] = C4_HOLD_REFUSED_*) leaves its slot byte for byte as it was -- InteractivePlay
+ * returning false -- and raises no error; so does a slot that is active, has visits to go and was asked no move.
+ * cols == NULL: no moves, just resume after a new target (temperatures and results must then be NULL).  temperatures == NULL: 1.0.
+ * results may be NULL.  The arrays have one entry per slot (n_slots) and may be device memory, pinned host memory or ordinary host
+ * memory (then the call copies and synchronises the stream); device or pinned arrays must stay untouched until the stream has passed
+ * the launch.  The reference's panics stay errors of the slot: C4_ERR_DEGENERATE_POLICY from a sampled move's weights. */
+int c4_session_hold_resume(c4_session* s, const int32_t* cols, const float* temperatures, int32_t* results);
+/* InteractivePlay::snapshot (interactive_play.rs:57, 145-166) of every slot, ONE launch and ONE copy: dst_host[slot] = (game_id, the
+ * root position, root_policy (mcts.rs:396-412), the root's q_sum / (visits + 1) (mcts.rs:359-367; the arithmetic of
+ * c4_session_root_stats), meta = moves made | 3 << 16), visits_host[slot] = the root's visit count, status_host[slot] = 0 idle (no
+ * game: record all zero), 1 active, C4_HOLD_PARKED, or the c4_status that ended the game.  From the mover's perspective (the
+ * player-0 view of interactive_play.rs:149-153 is the caller's to apply).  Host arrays of cap >= n_slots entries, any may be NULL.
+ * Synchronises. */
+int c4_session_snapshot(c4_session* s, c4_sample_rec* dst_host, uint32_t* visits_host, uint32_t* status_host, uint64_t cap);
+/* Non-blocking probe in the style of c4_session_poll: *n_active = the number of active slots and *max_need = the largest
+ * (target - root visits) any slot had at the last c4_session_hold_resume / c4_session_start -- a bound on the rounds still needed --
+ * as of the last probe that has landed; C4_HOLD_POLL_UNKNOWN for both until a probe enqueued after that resume has.  *error as
+ * c4_session_poll.  Any output may be NULL. */
+int c4_session_hold_poll(c4_session* s, uint32_t* n_active, uint32_t* max_need, uint32_t* error);
+
 /* Leaf position currently waiting for the evaluator, per slot (MctsGame::leaf_pos, mcts.rs:64-66);
- * status[g] = 1 active / 0 idle, ordinal[g] = index of the slot's game in reqs.  Host arrays of
+ * status[g] = 1 active / 0 idle (a hold session: or C4_HOLD_PARKED), ordinal[g] = index of the slot's game in reqs.  Host arrays of
  * n_slots (any may be NULL).  Synchronises.  Used by the numpy-callback compatibility mode. */
 int c4_session_leaves(c4_session* s, uint64_t* masks_host, uint64_t* values_host, uint32_t* status_host,
                       uint32_t* ordinals_host);
