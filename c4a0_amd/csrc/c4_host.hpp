@@ -2,14 +2,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/c4a0_hip.h"
+
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 
 namespace c4host {
 
-// The one error string behind c4_last_error_string() (thread-local, defined in c4_session.hip).
+// Sets the one error string behind c4_last_error_string() and returns `code` (the thread-local string and this function are
+// defined in c4_session.hip, beside c4_last_error_string itself).
 int fail(int code, const std::string& msg);
 
 // Entry points run on the device of their session / stream and leave the caller's current
@@ -54,4 +58,34 @@ inline hipError_t opt_in_lds(const void* kernel, int bytes, int device) {
   return e;
 }
 
+// The one way a run-time value becomes a template argument of a launch: f is called with a value of the type that stands for
+// it -- float / uint16_t for planes_dtype 0 / 1 (f32 / bf16 planes), std::true_type / std::false_type for a flag.  Whatever
+// combinations do not exist as kernels are refused BEFORE the dispatch: f is instantiated for every value it may be given.
+template <typename F>
+void with_planes(uint32_t planes_dtype, F&& f) {
+  if (planes_dtype == 0) f(float{}); else f(uint16_t{});
+}
+template <typename F>
+void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{}); else f(std::false_type{});
+}
+
+// one thread per element
+inline dim3 grid_for(uint64_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
+
 }  // namespace c4host
+
+// A HIP call inside an entry point: a failure ends the entry point with C4_ERR_HIP and "<the call>: <HIP's message>".
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess)                                                                          \
+      return c4host::fail(C4_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));          \
+  } while (0)
+
+// run the rest of the entry point on the session's device; the caller's current device is restored on return
+#define C4_ON_DEVICE(dev)                   \
+  c4host::DeviceGuard _device_guard(dev);   \
+  HIP_TRY(_device_guard.error())
+// ... or on the device a stream belongs to (entry points without a session)
+#define C4_ON_STREAM_DEVICE(stream) C4_ON_DEVICE(c4host::stream_device((hipStream_t)(stream)))

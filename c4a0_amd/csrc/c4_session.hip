@@ -22,6 +22,11 @@
 //
 // Bit-exactness: f32 arithmetic follows the reference operation by operation; this file is
 // compiled with -ffp-contract=off (see build.py) and uses the glibc expf/logf ports.
+//
+// This file: the step kernel family (everything step_body calls, bar the layout and the lane-group primitives of c4_tree.hpp) and
+// the session itself -- create / destroy, games, bindings, settings, start, the step launches, counters, progress.  Beside it:
+// c4_session_maint.hip (tail compaction, arena reclaim), c4_session_callback.hip (unique leaves for an evaluator outside the
+// device), c4_session_readout.hip (records, root statistics, hold snapshot) and c4_elementwise.hip (the parity kernels).
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stddef.h>
@@ -37,68 +42,14 @@
 #include "c4_device.hpp"
 #include "c4_head_out.hpp"
 #include "c4_host.hpp"
+#include "c4_session_impl.hpp"
 #include "c4_timeline.hpp"
+#include "c4_tree.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-// ------------------------------------------------------------------------------------------
-// HBM layout
-// ------------------------------------------------------------------------------------------
-struct __attribute__((aligned(16))) Entry {
-  uint32_t n;     // visit_count            (mcts.rs:335)
-  float q_pen;    // q_sum_penalty          (mcts.rs:336)
-  float q_nopen;  // q_sum_no_penalty       (mcts.rs:337)
-  float prior;    // initial_policy_value   (mcts.rs:338)
-};
-struct __attribute__((aligned(16))) Tail {
-  uint16_t child[7];  // per column: block holding that child's own children, 0 = not expanded (mcts.rs:339)
-  uint16_t legal;     // legal-move mask of the parent position (informational)
-};
-// The 7 children of an expanded node: ONE 128-byte line.  Lane c < 7 of a game's lane group loads
-// entry c, lane 7 the tail, in a single 16-byte-per-lane instruction; a backup touches one entry
-// (one 32-byte sector).  16-bit child links bound an arena to 65 535 blocks per slot.
-struct __attribute__((aligned(128))) Block {
-  Entry e[7];
-  Tail t;
-};
-constexpr uint32_t kMaxBlocksPerSlot = 65535;
-
-constexpr uint32_t kMaxPath = 43;   // root + at most 42 moves below it
-constexpr uint32_t kHotPath = 16;   // path levels kept in the slot's hot line
-// A resident game's state.  Everything a simulation needs is ONE 128-byte line, read by the game's
-// 8 lanes with one 16-byte-per-lane instruction at the start of the step kernel and written back
-// with one at the end (lane k owns dwords 4k..4k+3):
-//   lane 0: root position          lane 1: leaf position (waiting for the evaluator)
-//   lane 2: game id, ordinal, root visit count
-//   lane 3: state word, arena words, root ref, precomputed move RNG word
-//   lanes 4..7: the recorded path, TRANSPOSED: lane 4 + j holds levels j, j + 4, j + 8, j + 12, so
-//               the backup of level d runs on lane 4 + (d & 3) and the first four levels update in parallel
-// The second line holds path levels 16..42 (deep searches only).
-struct __attribute__((aligned(256))) Slot {
-  uint64_t root_mask, root_value;  // MctsGame::root position
-  uint64_t leaf_mask, leaf_value;  // MctsGame::leaf position
-  uint64_t game_id;
-  uint32_t ordinal;     // index into reqs / the sample store
-  uint32_t root_n;      // mirror of the root entry's visit count
-  uint32_t state;       // status[0:8] (0 idle, 1 active, >1 = c4_status error) | depth[8:16] (path[depth] = the leaf's entry)
-                        // | n_moves[16:24] | terminal_state of the leaf [24:26] | rng_for[26:32] (n_moves + 1 rng_word is for; 0 = none)
-  uint32_t arena;       // n_blocks[0:16] (bump pointer) | root_block[16:32] (the root's children block, 0 = not expanded)
-  uint32_t root_ref;    // (block << 3 | column) of the root's own entry
-  uint32_t rng_word;    // first ChaCha12 word for the NEXT move (mcts.rs:215-216), precomputed off the critical path
-  uint32_t path[kHotPath];        // entry refs of levels 0..15, transposed: path[4 * j + i] = level j + 4 * i
-  uint32_t path_deep[kMaxPath - kHotPath];   // levels 16..42
-  uint32_t pad_[32 - (kMaxPath - kHotPath)];
-};
-static_assert(sizeof(Slot) == 256 && offsetof(Slot, path) == 64 && offsetof(Slot, path_deep) == 128, "slot state: one hot line + the deep path");
-C4_DEV constexpr uint32_t slot_state(uint32_t status, uint32_t depth, uint32_t n_moves, uint32_t term, uint32_t rng_for) {
-  return status | (depth << 8) | (n_moves << 16) | (term << 24) | (rng_for << 26);
-}
-C4_DEV uint32_t slot_status(uint32_t state) { return state & 0xFFu; }
-static_assert(sizeof(Block) == 128 && sizeof(Entry) == 16 && sizeof(Tail) == 16 && sizeof(c4_sample_rec) == 64, "layout");
-
-enum : uint32_t { kIdle = 0, kActive = 1, kParked = C4_HOLD_PARKED };   // (kParked: hold sessions only, a status of its own)
 constexpr uint32_t kWavesPerTimingHelper = 1024;   // stamps one timing helper workgroup reduces
 
 // Diagnostic build only (-DC4_PHASE_STAMPS, tools/phase_profile.py): per-wavefront device-clock
@@ -120,58 +71,6 @@ constexpr uint32_t kWavesPerTimingHelper = 1024;   // stamps one timing helper w
 #define C4_STAMP(i, force) do { } while (0)
 #define C4_STAMP_ANY(i) do { } while (0)
 #endif
-enum : int { CTR_SIMS = 0, CTR_S, CTR_K, CTR_E, CTR_MOVES, CTR_DONE, CTR_SKIPPED, CTR_SAMPLES, CTR_PROBES, CTR_HITS, CTR_N = 16 };
-
-struct Globals {             // one small device struct of cross-wave words
-  unsigned long long queue_head;   // next game ordinal to start
-  unsigned long long games_done;
-  uint32_t error;            // first error status
-  uint32_t error_slot;
-  uint32_t hold_active;      // hold sessions (C4_FLAG_HOLD): slots whose status is active
-  uint32_t hold_need;        // ... and the largest n_iter - root visits among them at the last c4_session_hold_resume
-};
-
-struct Params {
-  Slot* slots;
-  Block* blocks;
-  unsigned long long* wave_ctr;  // [n_waves][CTR_N]
-  unsigned long long* stamps;    // [2][n_waves][2] start/end device clock of each wavefront, by launch parity
-  unsigned long long* clock_acc; // [0] sum of (last end - first start) over launches, [1] launches summed, [2..4] the timing helpers' scratch
-  uint32_t n_waves;
-  uint32_t seq;                  // launch sequence number
-  unsigned long long* phase;     // diagnostic build: [n_waves][16] phase stamps of the last launch
-  uint64_t* leaf_models;         // optional [n_slots]: model id that must evaluate each slot's leaf (mcts.rs:70-76)
-  Globals* glob;
-  const c4_game_metadata* reqs;
-  const uint64_t* start_mask;    // may be null
-  const uint64_t* start_value;
-  c4_sample_rec* samples;        // [n_games][43]
-  uint32_t* sample_counts;       // [n_games]
-  void* planes;
-  const float* logprobs;
-  const float* q;
-  unsigned long long n_games;
-  uint32_t n_slots;
-  uint32_t blocks_per_slot;
-  uint32_t n_iter;
-  float c_exploration;
-  float c_ply_penalty;
-  uint32_t flags;
-  float dir_alpha, dir_eps;       // Dirichlet root noise (extension); dir_eps == 0 disables
-  uint2* cache;                   // optional evaluation cache (extension): [cache_mask + 1] entries of 64 bytes, 8 x uint2
-  uint32_t cache_mask;
-  uint32_t max_sims;              // simulations one game may run in one launch (terminal / cached leaves need no evaluator)
-  const float* ln_tab;            // ln_tab[k] = c4_logf((float)k), k < n_ln: the parent-visit term of uct_value (mcts.rs:379)
-  uint32_t n_ln;
-  uint32_t half_blocks;           // reclaimed arenas (C4_FLAG_RECLAIM): blocks per half, blocks_per_slot = 2 x this; 0 = never-reclaimed arena
-  unsigned long long* reclaim_ctr;   // [2] passes, blocks copied (k_arena_reclaim)
-  // hold sessions (C4_FLAG_HOLD), read by k_hold_resume alone: per-slot moves (null = none), their temperatures, where the
-  // per-slot result codes go (may be null), and whether the launch is c4_session_start's (the slots were reset just now)
-  const int32_t* hold_cols;
-  const float* hold_temps;
-  int32_t* hold_results;
-  uint32_t hold_fresh;
-};
 
 // ------------------------------------------------------------------------------------------
 // Evaluation cache (extension, off by default): evaluator outputs keyed by position.
@@ -184,35 +83,6 @@ constexpr uint32_t kCacheMagic = 0xC4A0C4A0u;
 C4_DEV uint32_t cache_index(uint64_t mask, uint64_t value, uint32_t cache_mask) {
   const uint64_t h = (mask * 0x9E3779B97F4A7C15ull) ^ (value * 0xC2B2AE3D27D4EB4Full);
   return (uint32_t)(h >> 24) & cache_mask;
-}
-
-// ------------------------------------------------------------------------------------------
-// 8-lane group helpers
-// ------------------------------------------------------------------------------------------
-C4_DEV uint32_t shfl_u32(uint32_t v, int src_lane) { return (uint32_t)__shfl((int)v, src_lane, 64); }
-C4_DEV float shfl_f32(float v, int src_lane) { return __shfl(v, src_lane, 64); }
-
-// Exchanges inside an 8-lane group without the LDS crossbar (DPP): lane ^ 1, lane ^ 2, and 7 - lane.
-// After the first two every lane of a quad holds the quad's combination, so the mirror step pairs
-// the two quads: three steps reduce a group for any commutative, associative combination.
-template <int kStep>
-C4_DEV uint32_t grp_xchg(uint32_t v) {
-  static_assert(kStep >= 0 && kStep < 3, "three butterfly steps");
-  constexpr int ctrl = kStep == 0 ? 0xB1 /* quad_perm [1,0,3,2] */ : (kStep == 1 ? 0x4E /* quad_perm [2,3,0,1] */ : 0x141 /* row_half_mirror */);
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xF, 0xF, true);
-}
-template <int kStep>
-C4_DEV float grp_xchg(float v) { return __uint_as_float(grp_xchg<kStep>(__float_as_uint(v))); }
-
-// lane `sub` of a group loads its 16 bytes of block `blk`: entry `sub` (sub < 7) or the tail (sub == 7)
-C4_DEV uint4 load_block_lane(const Block* blocks, uint32_t blk, uint32_t sub) {
-  return reinterpret_cast<const uint4*>(blocks + blk)[sub];
-}
-// child link of column `col` out of the tail held by lane 7 of the group (col is group-uniform)
-C4_DEV uint32_t child_link(const uint4& raw, uint32_t col, int gbase) {
-  const uint32_t w = col >> 1;
-  const uint32_t mine = w == 0 ? raw.x : (w == 1 ? raw.y : (w == 2 ? raw.z : raw.w));
-  return (shfl_u32(mine, gbase + 7) >> (16u * (col & 1u))) & 0xFFFFu;
 }
 
 // Evaluation cache, lane-group side (entry layout at kCacheMagic).  `logit` = policy output `sub` on
@@ -339,22 +209,6 @@ C4_DEV uint32_t select_leaf(const Params& p, const Block* blocks, Slot* st, uint
   }
   leaf_mask = m; leaf_value = v; depth = d; leaf_ref = last_ref;
   return ((__ballot(nan_seen != 0) >> gbase) & 0xFFull) ? (uint32_t)C4_ERR_NAN_IN_TREE : 0u;
-}
-
-C4_DEV void raise_error(const Params& p, Slot* st, uint32_t g, uint32_t code) {
-  st->state = (st->state & ~0xFFu) | code;
-  if (atomicCAS(&p.glob->error, 0u, code) == 0u) p.glob->error_slot = g;
-}
-
-template <typename PlaneT>
-C4_DEV void store_plane(void* base, size_t idx, uint32_t bit);
-template <>
-C4_DEV void store_plane<float>(void* base, size_t idx, uint32_t bit) {
-  ((float*)base)[idx] = bit ? 1.0f : 0.0f;
-}
-template <>
-C4_DEV void store_plane<uint16_t>(void* base, size_t idx, uint32_t bit) {
-  ((uint16_t*)base)[idx] = bit ? (uint16_t)0x3F80 : (uint16_t)0;  // bf16 1.0 / 0.0
 }
 
 // A game's leaf as the evaluator's input row (c4r.rs:378-392): 84 elements, plane 0 = the bits of
@@ -1011,42 +865,6 @@ __global__ __launch_bounds__(64) void k_hold_resume(Params p) {
   step_body<PlaneT, false, false, false, true, true>(p, wave_index, lane, p.n_slots, st, hot, 0.0f, 0.0f, 0ull, g);
 }
 
-// c4_session_snapshot: InteractivePlay::snapshot (interactive_play.rs:57, 145-166) of every slot with a game, in ONE launch -- the
-// root position, root_policy (mcts.rs:396-412), the root's q as q_sum / (visits + 1) (mcts.rs:359-367: the arithmetic of
-// c4_session_root_stats and of a search record), the root's visit count and the slot's status.  8 lanes per slot.
-__global__ __launch_bounds__(64) void k_hold_snapshot(Params p, c4_sample_rec* dst, uint32_t* visits, uint32_t* status) {
-  const uint32_t lane = threadIdx.x & 63, sub = lane & 7;
-  const int gbase = (int)(lane & ~7u);
-  const uint32_t g = blockIdx.x * 8 + (lane >> 3);
-  const uint32_t gs = g < p.n_slots ? g : 0;
-  const Slot* st = p.slots + gs;
-  const Block* blocks = p.blocks + (size_t)gs * p.blocks_per_slot;
-  const uint32_t state = st->state, root_block = st->arena >> 16, root_ref = st->root_ref;
-  const bool game = slot_status(state) != kIdle;
-  const uint4 re = load_block_lane(blocks, game ? root_block : 0u, sub);
-  const float cnt = (game && sub < 7 && root_block != 0) ? (float)re.x : 0.0f;
-  float w[7];
-  float csum = 0.0f;
-  for (int i = 0; i < 7; i++) { w[i] = shfl_f32(cnt, gbase + i); csum = csum + w[i]; }
-  if (g >= p.n_slots) return;
-  c4_sample_rec* rec = dst + g;
-  if (!game) {
-    reinterpret_cast<uint2*>(rec)[sub] = make_uint2(0u, 0u);
-    if (sub == 7) { visits[g] = 0; status[g] = kIdle; }
-    return;
-  }
-  if (sub < 7) rec->policy[sub] = (csum == 0.0f) ? (1.0f / 7.0f) : (w[sub] / csum);
-  if (sub == 7) {
-    const Entry* re0 = &blocks[root_ref >> 3].e[root_ref & 7];
-    const float nf = (float)re0->n + 1.0f;
-    rec->game_id = st->game_id; rec->mask = st->root_mask; rec->value = st->root_value;
-    rec->q_penalty = re0->q_pen / nf; rec->q_no_penalty = re0->q_nopen / nf;
-    rec->meta = ((state >> 16) & 0xFFu) | (3u << 16);
-    visits[g] = re0->n;
-    status[g] = slot_status(state);
-  }
-}
-
 // c4_session_scatter_outputs + c4_session_step as ONE launch (callback mode, c4_session_step_gather): a game takes its evaluator
 // outputs from row inverse[g] of the callback's answers (7 log-probabilities, q_penalty, q_no_penalty per row; pinned host memory
 // or device memory) instead of from the bound tensors -- one launch and one boundary less per callback round trip.  The bound
@@ -1128,86 +946,10 @@ __global__ __launch_bounds__(64 * c4ho::kHeadWaves, 1) C4_OUT_STEP_ATTR void c4_
   C4_TL_END(3, a_slots);
 }
 
-// ------------------------------------------------------------------------------------------
-// Element-wise kernels (SURVEY 8a K1 and the arithmetic pieces) for the parity tests
-// ------------------------------------------------------------------------------------------
-__global__ void k_pos_ops(const uint64_t* mask, const uint64_t* value, const int32_t* col, uint64_t n, float c_ply,
-                          uint64_t* om, uint64_t* ov, uint32_t* olegal, uint32_t* oterm, float* oq) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t m = mask[i], v = value[i];
-  const uint32_t legal = c4::legal_mask(m);
-  const uint32_t t = c4::terminal_state(m, v);
-  float a = 0.0f, b = 0.0f;
-  if (t) c4::terminal_value(t, m, c_ply, a, b);
-  olegal[i] = legal;
-  oterm[i] = t;
-  oq[2 * i] = a;
-  oq[2 * i + 1] = b;
-  const int32_t c = col[i];
-  if (c >= 0 && c < 7 && ((legal >> c) & 1u)) {
-    c4::make_move(m, v, (uint32_t)c);
-    om[i] = m; ov[i] = v;
-  } else {
-    om[i] = 0; ov[i] = 0;  // make_move returns None (c4r.rs:71)
-  }
-}
-
-template <typename PlaneT>
-__global__ void k_encode(const uint64_t* mask, const uint64_t* value, uint64_t n, void* planes) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * C4_PLANES_LEN) return;
-  const uint64_t g = i / C4_PLANES_LEN;
-  const uint32_t e = (uint32_t)(i % C4_PLANES_LEN);
-  store_plane<PlaneT>(planes, i, c4::plane_bit(mask[g], value[g], e));
-}
-
-// ln_tab[k] = c4_logf((float)k): the same port the kernel would otherwise run per tree level
-__global__ void k_ln_table(float* tab, uint32_t n) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) tab[i] = c4::c4_logf((float)i);
-}
-
-__global__ void k_expf_logf(const float* x, uint64_t n, int which, float* y) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  y[i] = which ? c4::c4_logf(x[i]) : c4::c4_expf(x[i]);
-}
-
-__global__ void k_softmax7(const float* logits, const uint32_t* legal, uint64_t n, float* out, uint32_t* err) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float l[7], o[7];
-  for (int c = 0; c < 7; c++) {
-    l[c] = logits[7 * i + c];
-    if (legal && !((legal[i] >> c) & 1u)) l[c] = __uint_as_float(0xff800000u);
-  }
-  const bool ok = c4::softmax7(l, o);
-  err[i] = ok ? 0u : (uint32_t)C4_ERR_DEGENERATE_POLICY;
-  for (int c = 0; c < 7; c++) out[7 * i + c] = ok ? o[c] : 0.0f;
-}
-
-__global__ void k_temperature(const float* policy, const float* t, uint64_t n, float* out) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float p[7], o[7];
-  for (int c = 0; c < 7; c++) p[c] = policy[7 * i + c];
-  c4::apply_temperature(p, t[i], o);
-  for (int c = 0; c < 7; c++) out[7 * i + c] = o[c];
-}
-
-__global__ void k_sample_move(const uint64_t* game_id, const uint32_t* n_moves, const float* policy, const float* t,
-                              uint64_t n, int32_t* out_col, uint32_t* out_u32) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float p[7], o[7];
-  for (int c = 0; c < 7; c++) p[c] = policy[7 * i + c];
-  c4::apply_temperature(p, t[i], o);
-  const uint32_t u = c4::rng_first_u32(game_id[i] * (uint64_t)(42 + n_moves[i]));
-  out_col[i] = c4::weighted_index(o, u);
-  if (out_u32) out_u32[i] = u;
-}
-
+// The element-wise Dirichlet kernel (c4_dirichlet; its siblings are c4_elementwise.hip) stays in THIS file on purpose:
+// c4::dirichlet_noise is an out-of-line function the NOISE step kernels call, and hipcc specialises its body to the arguments of the
+// callers it sees.  This kernel passes an arbitrary `legal`; without it in the translation unit the function loses three instructions
+// (the 7-bit mask before the popcount) -- equivalent for the step kernels, but not the code that was measured.
 __global__ void k_dirichlet(const uint64_t* game_id, const uint32_t* n_moves, const uint32_t* legal, float alpha, uint64_t n, float* eta) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1216,311 +958,10 @@ __global__ void k_dirichlet(const uint64_t* game_id, const uint32_t* n_moves, co
   for (int c = 0; c < 7; c++) eta[7 * i + c] = e[c];
 }
 
-// ------------------------------------------------------------------------------------------
-// Tail compaction: once the request queue is empty, finished slots stay empty and the evaluator
-// would keep computing rows for them.  k_compact_plan pairs every active slot beyond the first A
-// slots (A = number of active games) with an idle slot below A; k_compact_move copies the game
-// (slot state, the used part of its arena, its evaluator input row) across.  All references inside
-// a game's state are arena-relative, so nothing needs patching.
-// ------------------------------------------------------------------------------------------
-struct CompactPlan {
-  uint32_t n_active;
-  uint32_t n_pairs;
-};
-__global__ __launch_bounds__(1024) void k_compact_plan(const Slot* slots, uint32_t n_slots, CompactPlan* plan, uint2* pairs) {
-  __shared__ uint32_t s_active, s_holes, s_movers;
-  if (threadIdx.x == 0) { s_active = 0; s_holes = 0; s_movers = 0; }
-  __syncthreads();
-  uint32_t mine = 0;
-  for (uint32_t g = threadIdx.x; g < n_slots; g += blockDim.x) mine += slot_status(slots[g].state) == kActive ? 1u : 0u;
-  atomicAdd(&s_active, mine);
-  __syncthreads();
-  const uint32_t A = s_active;
-  // any bijection between holes (< A, idle) and movers (>= A, active) will do: which slot plays a
-  // game changes nothing a game records
-  for (uint32_t g = threadIdx.x; g < n_slots; g += blockDim.x) {
-    const bool act = slot_status(slots[g].state) == kActive;
-    if (g < A && !act) pairs[atomicAdd(&s_holes, 1u)].y = g;
-    if (g >= A && act) pairs[atomicAdd(&s_movers, 1u)].x = g;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) { plan->n_active = A; plan->n_pairs = s_movers; }
-}
-
-template <typename PlaneT>
-__global__ __launch_bounds__(256) void k_compact_move(Params p, const CompactPlan* plan, const uint2* pairs) {
-  const uint32_t k = blockIdx.x;
-  if (k >= plan->n_pairs) return;
-  const uint32_t src = pairs[k].x, dst = pairs[k].y;
-  const Slot* ss = p.slots + src;
-  const uint32_t n_blocks = ss->arena & 0xFFFFu;
-  const uint4* sb = reinterpret_cast<const uint4*>(p.blocks + (size_t)src * p.blocks_per_slot);
-  uint4* db = reinterpret_cast<uint4*>(p.blocks + (size_t)dst * p.blocks_per_slot);
-  for (uint32_t i = threadIdx.x; i < n_blocks * 8u; i += blockDim.x) db[i] = sb[i];
-  PlaneT* pl = reinterpret_cast<PlaneT*>(p.planes);
-  for (uint32_t e = threadIdx.x; e < C4_PLANES_LEN; e += blockDim.x) pl[(size_t)dst * C4_PLANES_LEN + e] = pl[(size_t)src * C4_PLANES_LEN + e];
-  if (threadIdx.x < 16) reinterpret_cast<uint4*>(p.slots + dst)[threadIdx.x] = reinterpret_cast<const uint4*>(ss)[threadIdx.x];
-  __syncthreads();
-  if (threadIdx.x == 0) { p.slots[src].state = kIdle; p.slots[src].ordinal = 0xFFFFFFFFu; }
-}
-
-// ------------------------------------------------------------------------------------------
-// Reclaimed arenas (C4_FLAG_RECLAIM).  The reference drops the siblings' subtrees at every move (mcts.rs:187-206: the new
-// root's Rc is the only one left); the never-reclaimed arena keeps them, which is what bounds n_mcts_iterations by the 16-bit
-// child links (43 n + 8 <= 65 535 blocks).  Here a slot's arena is two halves of half_blocks blocks.  A game allocates in one of
-// them; when that half runs short, this kernel -- launched behind every reclaim_period-th step launch, between two steps, when
-// every game waits for the evaluator with a recorded path -- copies what is still reachable into the other half, compactly:
-//   new[0] = the block that holds the root's OWN entry (level 0 of every backup),  new[1] = the root's children block,
-//   then breadth first: the workgroup walks the copied blocks in order; a block's children are copied to the next free
-//   places and its links patched.  An old block's forwarding address goes into its tail's `legal` half-word (written by
-//   expansion, read by nobody), from which the recorded path (entry refs = block << 3 | column) is translated at the end.
-// Reachable blocks number at most (visits of the root + simulations of one launch + 2) <= half_blocks, so the copy always fits.
-// One workgroup of 1 024 threads per slot (128 lane groups of 8: a block is one 16-byte load per lane, as everywhere);
-// slots with room left return after one load.  Which block a node sits in changes nothing a game records.
-// ------------------------------------------------------------------------------------------
-constexpr int kReclaimThreads = 1024;
-constexpr uint32_t kReclaimSlotsPerGroup = 16;            // slots one workgroup looks at (a look is one 8-byte load; few slots ever need more)
-C4_DEV void reclaim_slot(const Params& p, uint32_t g, uint32_t min_free, uint32_t& s_tail, uint32_t& s_overflow);
-__global__ __launch_bounds__(kReclaimThreads) void k_arena_reclaim(Params p, uint32_t min_free) {
-  __shared__ uint32_t s_tail, s_overflow;
-  // one workgroup per 16 slots, one after the other (the test is workgroup-uniform): a launch that finds nothing to do is ~100
-  // workgroups that return after 16 loads, not one 1 024-thread workgroup per slot
-  for (uint32_t k = 0; k < kReclaimSlotsPerGroup; k++) {
-    const uint32_t g = blockIdx.x * kReclaimSlotsPerGroup + k;
-    if (g >= p.n_slots) return;
-    reclaim_slot(p, g, min_free, s_tail, s_overflow);
-    __syncthreads();
-  }
-}
-C4_DEV void reclaim_slot(const Params& p, const uint32_t g, const uint32_t min_free, uint32_t& s_tail, uint32_t& s_overflow) {
-  Slot* st = p.slots + g;
-  const uint32_t state = st->state, arena = st->arena;
-  if (slot_status(state) != kActive) return;
-  const uint32_t H = p.half_blocks;
-  const uint32_t n_blocks = arena & 0xFFFFu, root_block = arena >> 16;
-  const uint32_t cur = n_blocks > H ? H : 0u;             // the half in use (the upper one never holds fewer than H + 1)
-  if (H - (n_blocks - cur) >= min_free) return;           // room until the next look
-  Block* blocks = p.blocks + (size_t)g * p.blocks_per_slot;
-  const uint32_t dst = cur ? 0u : H;
-  const uint32_t tid = threadIdx.x, sub = tid & 7u, grp = tid >> 3;
-  const int gbase = (int)(tid & 63u & ~7u);
-  const uint32_t root_ref = st->root_ref, depth = (state >> 8) & 0xFFu;
-  if (grp == 0) reinterpret_cast<uint4*>(blocks + dst)[sub] = load_block_lane(blocks, root_ref >> 3, sub);
-  if (grp == 1 && root_block) {
-    reinterpret_cast<uint4*>(blocks + dst + 1)[sub] = load_block_lane(blocks, root_block, sub);
-    if (sub == 7) blocks[root_block].t.legal = (uint16_t)(dst + 1);
-  }
-  if (tid == 0) { s_tail = dst + (root_block ? 2u : 1u); s_overflow = 0u; }
-  __syncthreads();
-  uint32_t lo = dst + 1, hi = s_tail;
-  while (lo < hi) {                                       // one level of the tree per trip
-    for (uint32_t i = lo + grp; i < hi; i += kReclaimThreads / 8) {
-      const uint4 tl = sub == 7 ? load_block_lane(blocks, i, 7) : make_uint4(0, 0, 0, 0);   // the copied block's links are still OLD block numbers
-      uint32_t link[7], cnt = 0;
-#pragma unroll
-      for (int k = 0; k < 7; k++) {
-        const uint32_t w = k >> 1;
-        const uint32_t word = w == 0 ? tl.x : (w == 1 ? tl.y : (w == 2 ? tl.z : tl.w));
-        link[k] = (shfl_u32(word, gbase + 7) >> (16u * (k & 1u))) & 0xFFFFu;
-        cnt += link[k] ? 1u : 0u;
-      }
-      if (cnt == 0) continue;                             // (group-uniform)
-      uint32_t base = sub == 0 ? atomicAdd(&s_tail, cnt) : 0u;
-      base = shfl_u32(base, gbase);
-      // The host sizes the halves so that the live subtree always fits (reclaim_half_min); should that ever not hold (a damaged
-      // tree, a configuration changed under a running game), nothing is written past the destination half -- an upward copy
-      // would run into the NEXT slot's arena, a downward one into the half still being read -- and the slot raises the error the
-      // step kernel raises for a full arena, with its root, links and path left as they were.
-      if (base + cnt > dst + H) {                         // (group-uniform)
-        if (sub == 0) s_overflow = 1u;
-        continue;
-      }
-      uint4 v[7];
-#pragma unroll
-      for (int k = 0; k < 7; k++) if (link[k]) v[k] = load_block_lane(blocks, link[k], sub);
-      uint32_t r = 0, nl[7];
-#pragma unroll
-      for (int k = 0; k < 7; k++) {
-        nl[k] = 0;
-        if (link[k]) {
-          nl[k] = base + r++;
-          reinterpret_cast<uint4*>(blocks + nl[k])[sub] = v[k];
-          if (sub == 7) blocks[link[k]].t.legal = (uint16_t)nl[k];        // forwarding address (after the load above: one wavefront, program order)
-        }
-      }
-      if (sub == 7) {
-        uint4 t2 = tl;
-        t2.x = nl[0] | (nl[1] << 16); t2.y = nl[2] | (nl[3] << 16); t2.z = nl[4] | (nl[5] << 16); t2.w = nl[6] | (tl.w & 0xFFFF0000u);
-        reinterpret_cast<uint4*>(blocks + i)[7] = t2;
-      }
-    }
-    __syncthreads();                                      // this level's copies (and forwarding addresses) are visible to the workgroup
-    lo = hi; hi = s_tail;
-    if (s_overflow) hi = lo;                              // (workgroup-uniform: read between two barriers) stop walking
-    __syncthreads();
-  }
-  if (s_overflow) {
-    if (tid == 0) raise_error(p, st, g, C4_ERR_ARENA_OVERFLOW);
-    return;
-  }
-  // the recorded path: level L sits at path[4 (L & 3) + (L >> 2)] (L < 16) or path_deep[L - 16]; level 0 is the root's own entry
-  if (tid <= depth && tid < kMaxPath) {
-    uint32_t* slot_word = tid < kHotPath ? &st->path[4 * (tid & 3u) + (tid >> 2)] : &st->path_deep[tid - kHotPath];
-    const uint32_t ref = *slot_word;
-    *slot_word = tid == 0 ? ((dst << 3) | (root_ref & 7u)) : (((uint32_t)blocks[ref >> 3].t.legal << 3) | (ref & 7u));
-  }
-  if (tid == 0) {
-    st->root_ref = (dst << 3) | (root_ref & 7u);
-    st->arena = hi | ((root_block ? dst + 1u : 0u) << 16);
-    atomicAdd(&p.reclaim_ctr[0], 1ull);
-    atomicAdd(&p.reclaim_ctr[1], (unsigned long long)(hi - dst));
-  }
-}
-
-// Exclusive prefix sum of the per-game sample counts = where each game's records start in the packed
-// array.  One 1024-thread workgroup walks the list with a running carry (n_games is a few 10^4..10^6).
-__global__ __launch_bounds__(1024) void k_sample_offsets(const uint32_t* counts, unsigned long long n_games,
-                                                         unsigned long long* offsets, unsigned long long* total) {
-  __shared__ unsigned long long wave_sum[16];
-  __shared__ unsigned long long carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (unsigned long long base = 0; base < n_games; base += 1024) {
-    const unsigned long long i = base + tid;
-    const unsigned long long v = i < n_games ? counts[i] : 0ull;
-    unsigned long long x = v;                                   // inclusive scan inside the wavefront
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned long long y = ((unsigned long long)__shfl_up((int)(x >> 32), off, 64) << 32) | (uint32_t)__shfl_up((int)(uint32_t)x, off, 64);
-      if ((int)lane >= off) x += y;
-    }
-    if (lane == 63) wave_sum[wave] = x;
-    __syncthreads();
-    unsigned long long before = carry;                           // sums of the wavefronts before this one
-    for (uint32_t w = 0; w < wave; w++) before += wave_sum[w];
-    if (i < n_games) offsets[i] = before + x - v;
-    __syncthreads();
-    if (tid == 1023) carry = before + x;
-    __syncthreads();
-  }
-  if (tid == 0) *total = carry;
-}
-
-// Leaf keys for the callback evaluator's batching (NNThread::loop_once, self_play.rs:203-208: unique
-// (model, leaf position) pairs).  A position is its `value` bits (42) plus the 7 column heights
-// (3 bits each: the stones of a column stack from the bottom, so the heights determine `mask`):
-// 63 bits, one non-negative int64 per resident game; idle slots get -1.
-C4_DEV long long leaf_key_of(const Slot* st) {
-  if (slot_status(st->state) != kActive) return -1;
-  const uint64_t m = st->leaf_mask, v = st->leaf_value;
-  uint64_t heights = 0;
-  for (uint32_t c = 0; c < 7; c++) heights |= (uint64_t)__popcll(m & (c4::kCol0 << c)) << (3 * c);
-  return (long long)(v | (heights << 42));
-}
-
-__global__ void k_leaf_keys(const Slot* slots, uint32_t n_slots, long long* keys) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g < n_slots) keys[g] = leaf_key_of(slots + g);
-}
-
-// ---- the callback evaluator's batch on the device (NNThread::loop_once, self_play.rs:203-208) ----
-// The reference collects the waiting leaves in a HashSet<(model, Pos)> and evaluates each pair once.
-// Three small launches do the same for all resident games: (1) every slot enters an open-addressed
-// table of SLOT INDICES (a cell's pair is its slot's pair; slots with one pair meet in one cell and
-// keep the lowest index), (2) one workgroup ranks the representatives in slot order -- the batch's
-// row order depends on nothing but the games -- and maps every slot to its row, (3) the
-// representatives write their rows of the evaluator input ([2, 6, 7] float32, c4r.rs:378-392)
-// wherever the caller asked: normally pinned host memory, so the batch crosses PCIe once, written
-// by the kernel, and the host learns its size from one pinned word.
-constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
-constexpr uint32_t kRepFlag = 0x80000000u;
-
-__global__ void k_unique_insert(const Slot* slots, const uint64_t* leaf_models, uint32_t n_slots, uint32_t* tab,
-                                uint32_t tab_mask, uint32_t* cell) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_slots) return;
-  const long long key = leaf_key_of(slots + g);
-  if (key < 0) { cell[g] = kNoSlot; return; }
-  const uint64_t model = leaf_models ? leaf_models[g] : 0ull;
-  uint64_t x = ((uint64_t)key ^ (model * 0x9E3779B97F4A7C15ull)) * 0xD6E8FEB86659FD93ull;   // any mix does: only the
-  uint32_t h = (uint32_t)(x >> 32) & tab_mask;                                              // probe order depends on it
-  for (;;) {
-    const uint32_t cur = atomicCAS(&tab[h], kNoSlot, g);
-    if (cur == kNoSlot) break;                                     // first of its pair: this cell is the pair's
-    if (leaf_key_of(slots + cur) == key && (!leaf_models || leaf_models[cur] == model)) {
-      atomicMin(&tab[h], g);                                       // same pair: the lowest slot represents it
-      break;
-    }
-    h = (h + 1) & tab_mask;                                        // another pair's cell (cells never change pair)
-  }
-  cell[g] = h;
-}
-
-__global__ __launch_bounds__(1024) void k_unique_rank(const uint32_t* tab, const uint32_t* cell, uint32_t n_slots,
-                                                      uint32_t* row_of, uint32_t* inverse, uint32_t* n_unique_dev,
-                                                      uint32_t* n_unique_out) {
-  __shared__ uint32_t wave_sum[16];
-  __shared__ uint32_t carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t base = 0; base < n_slots; base += 1024) {
-    const uint32_t g = base + tid;
-    const bool rep = g < n_slots && cell[g] != kNoSlot && tab[cell[g]] == g;
-    const unsigned long long b = __ballot(rep);
-    if (lane == 0) wave_sum[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t before = carry;
-    for (uint32_t w = 0; w < wave; w++) before += wave_sum[w];
-    if (g < n_slots) row_of[g] = rep ? ((before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))) | kRepFlag) : 0u;
-    __syncthreads();
-    if (tid == 1023) carry = before + (uint32_t)__popcll(b);
-    __syncthreads();
-  }
-  __threadfence_block();
-  for (uint32_t g = tid; g < n_slots; g += 1024)
-    inverse[g] = cell[g] == kNoSlot ? kNoSlot : (row_of[tab[cell[g]]] & ~kRepFlag);
-  if (tid == 0) { *n_unique_dev = carry; *n_unique_out = carry; }
-}
-
-// one wavefront per slot; also hands the table back empty (nothing reads it here)
-__global__ __launch_bounds__(256) void k_unique_emit(const Slot* slots, const uint64_t* leaf_models, uint32_t n_slots,
-                                                     uint32_t* tab, const uint32_t* cell, const uint32_t* row_of,
-                                                     float* rows_out, uint64_t* models_out) {
-  const uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (g >= n_slots) return;
-  const uint32_t c = cell[g];
-  if (c == kNoSlot) return;
-  if (lane == 0) tab[c] = kNoSlot;
-  const uint32_t r = row_of[g];
-  if (!(r & kRepFlag)) return;
-  const uint32_t row = r & ~kRepFlag;
-  const uint64_t m = slots[g].leaf_mask, v = slots[g].leaf_value;
-  for (uint32_t e = lane; e < C4_PLANES_LEN; e += 64) rows_out[(size_t)row * C4_PLANES_LEN + e] = c4::plane_bit(m, v, e) ? 1.0f : 0.0f;
-  if (models_out && lane == 0) models_out[row] = leaf_models ? leaf_models[g] : 0ull;
-}
-
-// the evaluator's answers back to every slot that asked: answers[row] = 7 log-probabilities, q_penalty, q_no_penalty
-__global__ void k_unique_scatter(const uint32_t* inverse, const float* answers, uint32_t n_slots, uint32_t n_unique,
-                                 float* logprobs, float* q) {
+// ln_tab[k] = c4_logf((float)k): the same port the kernel would otherwise run per tree level
+__global__ void k_ln_table(float* tab, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t g = i / 9, e = i % 9;
-  if (g >= n_slots) return;
-  const uint32_t row = inverse[g];
-  if (row >= n_unique) return;                                     // idle slot
-  const float a = answers[(size_t)row * 9 + e];
-  if (e < 7) logprobs[(size_t)g * 7 + e] = a; else q[(size_t)g * 2 + (e - 7)] = a;
-}
-
-// K6: pack finished games' records contiguously (one wavefront per game, 4 records per pass)
-__global__ __launch_bounds__(64) void k_pack_samples(const c4_sample_rec* src, const uint32_t* counts,
-                                                     const unsigned long long* offsets, uint64_t n_games, c4_sample_rec* dst) {
-  const uint64_t game = blockIdx.x;
-  if (game >= n_games) return;
-  const uint32_t n = counts[game];
-  const uint4* s4 = (const uint4*)(src + game * C4_MAX_SAMPLES_PER_GAME);
-  uint4* d4 = (uint4*)(dst + offsets[game]);
-  for (uint32_t i = threadIdx.x; i < n * 4u; i += 64) d4[i] = s4[i];  // 64-byte record = 4 x 16 bytes
+  if (i < n) tab[i] = c4::c4_logf((float)i);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1528,104 +969,9 @@ __global__ __launch_bounds__(64) void k_pack_samples(const c4_sample_rec* src, c
 // ------------------------------------------------------------------------------------------
 thread_local std::string g_last_error;
 using c4host::fail;
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess)                                                                          \
-      return fail(C4_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                  \
-  } while (0)
-
-}  // namespace
-
-int c4host::fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  // HIP keeps a failed call's code as the thread's "last error" until somebody reads it; the launch checks of this library read it
-  // (hipGetLastError after every launch), so a failed hipMalloc of ONE call -- device memory full -- used to surface as "out of
-  // memory" in the next call's first launch, long after the memory was there again.  The failure is reported here: take it off.
-  if (code == C4_ERR_HIP) (void)hipGetLastError();
-  return code;
-}
-
-// run the rest of the entry point on the session's device; the caller's current device is restored on return
-#define C4_ON_DEVICE(dev)                   \
-  c4host::DeviceGuard _device_guard(dev);   \
-  HIP_TRY(_device_guard.error())
-
-struct c4_session {
-  c4_config cfg{};
-  Params p{};
-  hipStream_t stream = nullptr;
-  uint32_t lanes_per_game = 8;   // c4_step_kernel's mapping (a 4-lane variant was built and measured: tools/experiments/)
-  uint32_t n_waves = 0;       // wavefronts a step launches now (shrinks with c4_session_compact)
-  uint32_t out_step_gpw = 8;  // games per stepping wavefront of the fused output + step launch (c4_session_set_step_shape)
-  uint32_t n_waves_cap = 0;   // as created: size of the per-wavefront arrays
-  uint32_t seq = 0;
-  bool timing = true;
-  bool bound = false, have_games = false;
-  uint64_t n_games = 0;
-  c4_game_metadata* reqs_dev = nullptr;
-  uint64_t* start_mask_dev = nullptr;
-  uint64_t* start_value_dev = nullptr;
-  // pinned probe buffer for c4_session_poll
-  Globals* probe_host = nullptr;
-  hipEvent_t probe_event = nullptr;
-  bool probe_pending = false;
-  uint64_t probe_done = 0;
-  uint64_t probe_started = 0;
-  uint32_t probe_error = 0;
-  CompactPlan* plan_dev = nullptr;   // tail compaction scratch
-  uint2* pairs_dev = nullptr;
-  float* ln_tab_dev = nullptr;                 // ln(visit count) table of select (Params::ln_tab)
-  unsigned long long* offsets_dev = nullptr;   // pack_samples: [n_games] record offsets + [1] total, sized by set_games
-  unsigned long long* total_host = nullptr;    // pinned
-  // c4_session_unique_leaves scratch (first use): table of slot indices, each slot's cell, its row, the count
-  size_t arena_bytes = 0;                      // of p.blocks (kept for the next session when this one is destroyed)
-  uint32_t* uniq_tab = nullptr;
-  uint32_t uniq_tab_mask = 0;
-  uint32_t* uniq_cell = nullptr;
-  uint32_t* uniq_row = nullptr;
-  uint32_t* uniq_count = nullptr;
-  // reclaimed arenas (C4_FLAG_RECLAIM): step launches since the last look at the arenas, and the capture they were counted in
-  uint32_t reclaim_period = 0;
-  uint32_t reclaim_count = 0;
-  unsigned long long reclaim_capture_id = 0;
-  // hold sessions (C4_FLAG_HOLD): staging for per-slot arrays handed over in pageable host memory (cols, temperatures, results),
-  // the snapshot's device and pinned buffers, and the active-slot probe (valid once a probe enqueued after the last resume landed)
-  int32_t* hold_cols_dev = nullptr;
-  float* hold_temps_dev = nullptr;
-  int32_t* hold_results_dev = nullptr;
-  unsigned char* snap_dev = nullptr;
-  unsigned char* snap_host = nullptr;
-  uint32_t hold_epoch = 0, probe_epoch = 0;
-  bool hold_probe_valid = false;
-  uint32_t hold_probe_active = 0, hold_probe_need = 0;
-};
-
-C4_TL_SETTER(c4_debug_timeline_session)
-
-extern "C" {
-
-const char* c4_last_error_string(void) { return g_last_error.c_str(); }
-int c4_abi_version(void) { return C4_ABI_VERSION; }
-
-#ifndef C4_SOURCE_HASH
-#define C4_SOURCE_HASH "unknown"
-#endif
-// content hash of the sources this library was compiled from (c4a0_amd/csrc/build.py); the marker
-// prefix lets the build script read it from the file's bytes without loading the library
-const char* c4_source_hash(void) {
-  static const char marked[] = "c4a0-src-hash:" C4_SOURCE_HASH;
-  return marked + 14;
-}
-
-int c4_device_count(int* out) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) n = 0;
-  if (out) *out = n;
-  return C4_OK;
-}
+using c4host::grid_for;
+using c4host::with_flag;
+using c4host::with_planes;
 
 // The tree arena is by far a session's largest allocation (13 GB for the reference's default job: 1 700 slots x
 // (43 x 1 400 + 8) blocks) and the driver scrubs freed device memory before it hands it out again: a session created
@@ -1633,7 +979,6 @@ int c4_device_count(int* out) {
 // per process is therefore kept for the next session on the same device that fits it (no more than twice as big as
 // needed); nothing in it is ever read before it is written (blocks are bump-allocated per slot, c4_start_kernel
 // writes each slot's root).  c4_trim_cached_memory() gives it back; C4_ARENA_CACHE=0 switches the cache off.
-namespace {
 struct ArenaCache { void* ptr = nullptr; size_t bytes = 0; int device = -1; };
 ArenaCache g_arena_cache;
 std::mutex g_arena_mutex;
@@ -1685,45 +1030,6 @@ void arena_release(int device, void* ptr, size_t bytes) {
   }
   if (drop) (void)hipFree(drop);
 }
-}  // namespace
-
-// ---- reclaimed arenas (C4_FLAG_RECLAIM, k_arena_reclaim) ----
-constexpr uint32_t kReclaimPeriod = 64;          // step launches between two looks at the arenas
-constexpr uint32_t kReclaimAuto = 1000;          // blocks_per_slot == 0: reclaim above this many iterations per move
-constexpr uint32_t kReclaimMaxSims = 8;          // simulations one game may run per launch in a reclaimed arena (evaluation cache)
-// A half is compacted when fewer than this many blocks are free in it.  Between two looks a game takes at most
-// max_sims blocks per step launch, and two looks are at most 2 x period launches apart (an eager step sequence that runs
-// into a graph replay, or the other way round: each form alone keeps the period, see maybe_reclaim).
-static uint32_t reclaim_min_free(uint32_t period, uint32_t max_sims) { return 2u * period * max_sims + 16u; }
-// What a half must hold at the very least: the live subtree right after a compaction (<= n + max_sims + 2 blocks, + slack) and
-// twice the trigger above, so that a freshly compacted half is not at its next trigger already.
-static uint64_t reclaim_half_min(uint32_t n_iter, uint32_t period, uint32_t max_sims) {
-  return (uint64_t)n_iter + max_sims + 8u + 2ull * reclaim_min_free(period, max_sims);
-}
-static bool reclaim_mode(const c4_config* cfg) {
-  return (cfg->flags & C4_FLAG_RECLAIM) != 0 ||
-         (cfg->blocks_per_slot == 0 && cfg->n_mcts_iterations > kReclaimAuto && !(cfg->flags & (C4_FLAG_NO_MOVES | C4_FLAG_NO_RECLAIM | C4_FLAG_SEARCH | C4_FLAG_HOLD)));
-}
-static bool search_mode(const c4_session* s) { return (s->cfg.flags & C4_FLAG_SEARCH) != 0; }
-static bool hold_mode(const c4_session* s) { return (s->cfg.flags & C4_FLAG_HOLD) != 0; }
-
-// Called behind every step launch of a reclaimed session: every `period`-th launch is followed by k_arena_reclaim on the same
-// stream.  Launches are counted per capture while the stream is being captured into a HIP graph (the count restarts with the
-// capture, so EVERY graph carries a look behind its first step and every `period` steps after it: replays never run longer
-// than min(period, graph length) steps without one), and continuously otherwise.
-static int maybe_reclaim(c4_session* s) {
-  if (!s->p.half_blocks) return C4_OK;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  unsigned long long id = 0;
-  if (hipStreamGetCaptureInfo(s->stream, &cs, &id) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; id = 0; }
-  if (cs != hipStreamCaptureStatusActive) id = 0;
-  if (id != s->reclaim_capture_id) { s->reclaim_capture_id = id; s->reclaim_count = 0; }
-  if (s->reclaim_count++ % s->reclaim_period != 0) return C4_OK;
-  hipLaunchKernelGGL(k_arena_reclaim, dim3((s->p.n_slots + kReclaimSlotsPerGroup - 1) / kReclaimSlotsPerGroup), dim3(kReclaimThreads), 0, s->stream, s->p,
-                     reclaim_min_free(s->reclaim_period, s->p.max_sims));
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
 
 static hipError_t reset_clock_acc(unsigned long long* acc_dev) {
   const unsigned long long init[5] = {0ull, 0ull, ~0ull, 0ull, 0ull};   // totals; running min start, max end, helpers done
@@ -1751,9 +1057,7 @@ static int session_create_on_device(const c4_config* cfg, c4_session* s) {
   }
   s->cfg.blocks_per_slot = (uint32_t)bps;
   const size_t n = cfg->n_slots;
-  const uint32_t games_per_wave = 64u / s->lanes_per_game;
-  s->n_waves = (uint32_t)((n + games_per_wave - 1) / games_per_wave);
-  s->n_waves_cap = (uint32_t)((n + 7) / 8);   // per-wavefront arrays are sized for the finer kernel
+  s->n_waves = s->n_waves_cap = (uint32_t)((n + kGamesPerWave - 1) / kGamesPerWave);
   Params& p = s->p;
   p.n_slots = cfg->n_slots;
   p.blocks_per_slot = (uint32_t)bps;
@@ -1796,6 +1100,115 @@ static int session_create_on_device(const c4_config* cfg, c4_session* s) {
   HIP_TRY(hipMemset(p.reclaim_ctr, 0, 2 * sizeof(unsigned long long)));
   HIP_TRY(hipMemset(p.wave_ctr, 0, (size_t)s->n_waves_cap * CTR_N * sizeof(unsigned long long)));
   memset(s->probe_host, 0, sizeof(Globals));
+  return C4_OK;
+}
+
+// k_hold_resume on the session's stream: the arrays are device views (or null); fresh = c4_session_start's launch
+static int hold_launch_resume(c4_session* s, const int32_t* cols, const float* temps, int32_t* results, bool fresh) {
+  Params q = s->p;
+  q.seq = 0;
+  q.hold_cols = cols; q.hold_temps = temps; q.hold_results = results; q.hold_fresh = fresh ? 1u : 0u;
+  s->hold_epoch++;   // what a probe enqueued before this point saw is history
+  s->hold_probe_valid = false;
+  HIP_TRY(hipMemsetAsync(&s->p.glob->hold_need, 0, sizeof(uint32_t), s->stream));
+  if (fresh) HIP_TRY(hipMemsetAsync(&s->p.glob->hold_active, 0, sizeof(uint32_t), s->stream));   // every slot is counted anew
+  with_planes(s->cfg.planes_dtype, [&](auto planes) {
+    hipLaunchKernelGGL(k_hold_resume<decltype(planes)>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, q);
+  });
+  HIP_TRY(hipGetLastError());
+  return C4_OK;
+}
+
+static int launch_step(c4_session* s, const uint32_t* inverse, const float* answers, uint32_t n_unique) {
+  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
+  if (!s->bound || !s->have_games) return fail(C4_ERR_NOT_BOUND, "bind_io and set_games must precede step");
+  C4_ON_DEVICE(s->cfg.device);
+  // launch sequence number for the device-clock stamps; frozen at 0 (= no per-launch timing) when
+  // timing is off, which is what a launch captured into a HIP graph needs (arguments are baked in)
+  s->p.seq = s->timing ? ++s->seq : 0;
+  // the Dirichlet-noise and evaluation-cache extensions are separate instantiations: the default
+  // kernel carries none of their registers or scratch
+  const bool noise = s->p.dir_eps > 0.0f, cache = s->p.cache != nullptr;
+#ifdef C4_DIAG_VARIANTS
+  // C4_STEP_LDS_BYTES (diagnostic build only, tools/occupancy_probe.sh): unused dynamic LDS per workgroup caps the
+  // wavefronts a CU holds (160 KB / bytes) without touching the code: how the launch time scales with occupancy
+  static const unsigned lds_pad = [] { const char* e = getenv("C4_STEP_LDS_BYTES"); return e ? (unsigned)atoi(e) : 0u; }();
+#else
+  constexpr unsigned lds_pad = 0;
+#endif
+  // a timed launch (seq != 0) carries extra workgroups that fold the previous launch's stamps
+  const uint32_t helpers = s->p.seq ? (s->n_waves + kWavesPerTimingHelper - 1) / kWavesPerTimingHelper : 0u;
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(s->n_waves + helpers), dim3(64), lds_pad, s->stream, s->p.slots, s->p.logprobs, s->p.q, s->p.n_waves, s->p.n_slots, s->p);
+  };
+  auto launch_gather = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(s->n_waves + helpers), dim3(64), lds_pad, s->stream, s->p.slots, answers, inverse, n_unique, s->p.n_waves, s->p.n_slots, s->p);
+  };
+  // mode -> (NOISE, CACHE, SEARCH, HOLD) -> kernel.  A search and a hold session have ONE step kernel each: no noise, cache or
+  // gather form (refused where they are asked for).
+  with_planes(s->cfg.planes_dtype, [&](auto planes) {
+    using P = decltype(planes);
+    if (search_mode(s)) launch(c4_step_kernel<P, false, false, true>);
+    else if (hold_mode(s)) launch(c4_step_kernel<P, false, false, false, true>);
+    else with_flag(noise, [&](auto n) { with_flag(cache, [&](auto c) {
+      constexpr bool NOISE = decltype(n)::value, CACHE = decltype(c)::value;
+      if (inverse) launch_gather(c4_step_gather_kernel<P, NOISE, CACHE>); else launch(c4_step_kernel<P, NOISE, CACHE>);
+    }); });
+  });
+  HIP_TRY(hipGetLastError());
+  return maybe_reclaim(s);
+}
+
+// One per-slot array of c4_session_hold_resume as the kernel may use it: device memory and pinned host memory through
+// device_view; pageable host memory (what HIP does not know) through the session's staging buffer `stage` (copied in now when
+// `copy_in`).  *staged tells the caller which.
+static int hold_array(c4_session* s, const void* ptr, void** stage, bool copy_in, const char* what, void** out, bool* staged) {
+  const size_t bytes = (size_t)s->cfg.n_slots * 4;
+  *staged = false;
+  hipPointerAttribute_t attr{};
+  const hipError_t e = hipPointerGetAttributes(&attr, ptr);
+  if (e == hipSuccess && attr.type != hipMemoryTypeUnregistered) return device_view(ptr, s->cfg.device, what, out);
+  if (e != hipSuccess) (void)hipGetLastError();
+  if (!*stage) HIP_TRY(hipMalloc(stage, bytes));
+  if (copy_in) HIP_TRY(hipMemcpyAsync(*stage, ptr, bytes, hipMemcpyHostToDevice, s->stream));
+  *out = *stage;
+  *staged = true;
+  return C4_OK;
+}
+
+}  // namespace
+
+int c4host::fail(int code, const std::string& msg) {
+  g_last_error = msg;
+  // HIP keeps a failed call's code as the thread's "last error" until somebody reads it; the launch checks of this library read it
+  // (hipGetLastError after every launch), so a failed hipMalloc of ONE call -- device memory full -- used to surface as "out of
+  // memory" in the next call's first launch, long after the memory was there again.  The failure is reported here: take it off.
+  if (code == C4_ERR_HIP) (void)hipGetLastError();
+  return code;
+}
+
+C4_TL_SETTER(c4_debug_timeline_session)
+
+extern "C" {
+
+const char* c4_last_error_string(void) { return g_last_error.c_str(); }
+int c4_abi_version(void) { return C4_ABI_VERSION; }
+
+#ifndef C4_SOURCE_HASH
+#define C4_SOURCE_HASH "unknown"
+#endif
+// content hash of the sources this library was compiled from (c4a0_amd/csrc/build.py); the marker
+// prefix lets the build script read it from the file's bytes without loading the library
+const char* c4_source_hash(void) {
+  static const char marked[] = "c4a0-src-hash:" C4_SOURCE_HASH;
+  return marked + 14;
+}
+
+int c4_device_count(int* out) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess) n = 0;
+  if (out) *out = n;
   return C4_OK;
 }
 
@@ -1923,7 +1336,7 @@ int c4_session_set_games(c4_session* s, const c4_game_metadata* reqs, uint64_t n
     HIP_TRY(hipMemcpy(s->start_value_dev, start_values, n_games * 8, hipMemcpyHostToDevice));
   }
   s->p.n_slots = s->cfg.n_slots;   // a compacted session goes back to its full width
-  s->n_waves = s->p.n_waves = (s->cfg.n_slots + 64u / s->lanes_per_game - 1) / (64u / s->lanes_per_game);
+  s->n_waves = s->p.n_waves = (s->cfg.n_slots + kGamesPerWave - 1) / kGamesPerWave;
   Globals g0{};
   g0.queue_head = n_games < s->cfg.n_slots ? n_games : s->cfg.n_slots;
   HIP_TRY(hipMemcpy(s->p.glob, &g0, sizeof g0, hipMemcpyHostToDevice));
@@ -1982,8 +1395,7 @@ int c4_session_bind_io(c4_session* s, void* planes_dev, const float* logprobs_de
 int c4_session_set_dirichlet(c4_session* s, float alpha, float epsilon) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (!(epsilon >= 0.0f && epsilon <= 1.0f) || (epsilon > 0.0f && !(alpha > 0.0f))) return fail(C4_ERR_BAD_ARG, "need 0 <= epsilon <= 1 and alpha > 0");
-  if (epsilon > 0.0f && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_dirichlet: a search session (C4_FLAG_SEARCH) has no Dirichlet-noise step kernel");
-  if (epsilon > 0.0f && hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_dirichlet: a hold session (C4_FLAG_HOLD) has no Dirichlet-noise step kernel");
+  if (epsilon > 0.0f) if (int rc = refuse_search_hold(s, "c4_session_set_dirichlet", "has no Dirichlet-noise step kernel")) return rc;
   s->p.dir_alpha = alpha;
   s->p.dir_eps = epsilon;
   return C4_OK;
@@ -1991,8 +1403,7 @@ int c4_session_set_dirichlet(c4_session* s, float alpha, float epsilon) {
 
 int c4_session_bind_leaf_models(c4_session* s, uint64_t* leaf_models_dev) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
-  if (leaf_models_dev && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_bind_leaf_models: a search session (C4_FLAG_SEARCH) has ONE evaluator");
-  if (leaf_models_dev && hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_bind_leaf_models: a hold session (C4_FLAG_HOLD) has ONE evaluator (a match is two sessions exchanging moves)");
+  if (leaf_models_dev) if (int rc = refuse_search_hold(s, "c4_session_bind_leaf_models", "has ONE evaluator", " (a match is two sessions exchanging moves)")) return rc;
   if (leaf_models_dev && s->p.cache) return fail(C4_ERR_BAD_ARG, "the evaluation cache holds ONE evaluator's outputs: not with multi-model games");
   s->p.leaf_models = leaf_models_dev;
   return C4_OK;
@@ -2002,8 +1413,7 @@ int c4_session_set_eval_cache(c4_session* s, uint64_t n_entries, uint32_t max_si
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (n_entries && s->p.leaf_models) return fail(C4_ERR_BAD_ARG, "the evaluation cache holds ONE evaluator's outputs: not with multi-model games");
   if (n_entries > (1ull << 31)) return fail(C4_ERR_BAD_ARG, "at most 2^31 cache entries");
-  if (n_entries && search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_eval_cache: a search session (C4_FLAG_SEARCH) has no evaluation-cache step kernel");
-  if (n_entries && hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_eval_cache: a hold session (C4_FLAG_HOLD) has no evaluation-cache step kernel");
+  if (n_entries) if (int rc = refuse_search_hold(s, "c4_session_set_eval_cache", "has no evaluation-cache step kernel")) return rc;
   C4_ON_DEVICE(s->cfg.device);
   HIP_TRY(hipStreamSynchronize(s->stream));
   (void)hipFree(s->p.cache);
@@ -2029,88 +1439,23 @@ int c4_session_set_eval_cache(c4_session* s, uint64_t n_entries, uint32_t max_si
   return C4_OK;
 }
 
-// k_hold_resume on the session's stream: the arrays are device views (or null); fresh = c4_session_start's launch
-static int hold_launch_resume(c4_session* s, const int32_t* cols, const float* temps, int32_t* results, bool fresh) {
-  Params q = s->p;
-  q.seq = 0;
-  q.hold_cols = cols; q.hold_temps = temps; q.hold_results = results; q.hold_fresh = fresh ? 1u : 0u;
-  s->hold_epoch++;   // what a probe enqueued before this point saw is history
-  s->hold_probe_valid = false;
-  HIP_TRY(hipMemsetAsync(&s->p.glob->hold_need, 0, sizeof(uint32_t), s->stream));
-  if (fresh) HIP_TRY(hipMemsetAsync(&s->p.glob->hold_active, 0, sizeof(uint32_t), s->stream));   // every slot is counted anew
-  if (s->cfg.planes_dtype == 0) hipLaunchKernelGGL(k_hold_resume<float>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, q);
-  else hipLaunchKernelGGL(k_hold_resume<uint16_t>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, q);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
 int c4_session_start(c4_session* s) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (!s->bound || !s->have_games) return fail(C4_ERR_NOT_BOUND, "bind_io and set_games must precede start");
   C4_ON_DEVICE(s->cfg.device);
   if (hold_mode(s)) return hold_launch_resume(s, nullptr, nullptr, nullptr, true);   // reset_slot + the one kernel that makes a game active
-  if (s->cfg.planes_dtype == 0)
-    hipLaunchKernelGGL(c4_start_kernel<float>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, s->p);
-  else
-    hipLaunchKernelGGL(c4_start_kernel<uint16_t>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, s->p);
+  with_planes(s->cfg.planes_dtype, [&](auto planes) {
+    hipLaunchKernelGGL(c4_start_kernel<decltype(planes)>, dim3((s->p.n_slots + 7) / 8), dim3(64), 0, s->stream, s->p);
+  });
   HIP_TRY(hipGetLastError());
   return C4_OK;
-}
-
-static int device_view(const void* ptr, int device, const char* what, void** out);   // defined with the callback-mode entry points below
-
-static int launch_step(c4_session* s, const uint32_t* inverse, const float* answers, uint32_t n_unique) {
-  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
-  if (!s->bound || !s->have_games) return fail(C4_ERR_NOT_BOUND, "bind_io and set_games must precede step");
-  C4_ON_DEVICE(s->cfg.device);
-  // launch sequence number for the device-clock stamps; frozen at 0 (= no per-launch timing) when
-  // timing is off, which is what a launch captured into a HIP graph needs (arguments are baked in)
-  s->p.seq = s->timing ? ++s->seq : 0;
-  // the Dirichlet-noise and evaluation-cache extensions are separate instantiations: the default
-  // kernel carries none of their registers or scratch
-  const bool noise = s->p.dir_eps > 0.0f, cache = s->p.cache != nullptr;
-#ifdef C4_DIAG_VARIANTS
-  // C4_STEP_LDS_BYTES (diagnostic build only, tools/occupancy_probe.sh): unused dynamic LDS per workgroup caps the
-  // wavefronts a CU holds (160 KB / bytes) without touching the code: how the launch time scales with occupancy
-  static const unsigned lds_pad = [] { const char* e = getenv("C4_STEP_LDS_BYTES"); return e ? (unsigned)atoi(e) : 0u; }();
-#else
-  constexpr unsigned lds_pad = 0;
-#endif
-  // a timed launch (seq != 0) carries extra workgroups that fold the previous launch's stamps
-  const uint32_t helpers = s->p.seq ? (s->n_waves + kWavesPerTimingHelper - 1) / kWavesPerTimingHelper : 0u;
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(s->n_waves + helpers), dim3(64), lds_pad, s->stream, s->p.slots, s->p.logprobs, s->p.q, s->p.n_waves, s->p.n_slots, s->p);
-  };
-  auto launch_gather = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(s->n_waves + helpers), dim3(64), lds_pad, s->stream, s->p.slots, answers, inverse, n_unique, s->p.n_waves, s->p.n_slots, s->p);
-  };
-  const bool f32 = s->cfg.planes_dtype == 0;
-#define C4_LAUNCH_STEP(KERNEL, LAUNCH)                                                                               \
-  do {                                                                                                               \
-    if (f32) {                                                                                                       \
-      if (noise) { if (cache) LAUNCH(KERNEL<float, true, true>); else LAUNCH(KERNEL<float, true, false>); }          \
-      else       { if (cache) LAUNCH(KERNEL<float, false, true>); else LAUNCH(KERNEL<float, false, false>); }        \
-    } else {                                                                                                         \
-      if (noise) { if (cache) LAUNCH(KERNEL<uint16_t, true, true>); else LAUNCH(KERNEL<uint16_t, true, false>); }    \
-      else       { if (cache) LAUNCH(KERNEL<uint16_t, false, true>); else LAUNCH(KERNEL<uint16_t, false, false>); }  \
-    }                                                                                                                \
-  } while (0)
-  if (search_mode(s)) {   // no noise, cache or gather form (refused where they are asked for)
-    if (f32) launch(c4_step_kernel<float, false, false, true>); else launch(c4_step_kernel<uint16_t, false, false, true>);
-  } else if (hold_mode(s)) {   // likewise
-    if (f32) launch(c4_step_kernel<float, false, false, false, true>); else launch(c4_step_kernel<uint16_t, false, false, false, true>);
-  } else if (inverse) C4_LAUNCH_STEP(c4_step_gather_kernel, launch_gather); else C4_LAUNCH_STEP(c4_step_kernel, launch);
-#undef C4_LAUNCH_STEP
-  HIP_TRY(hipGetLastError());
-  return maybe_reclaim(s);
 }
 
 int c4_session_step(c4_session* s) { return launch_step(s, nullptr, nullptr, 0); }
 
 int c4_session_step_gather(c4_session* s, const uint32_t* inverse_dev, const float* answers, uint32_t n_unique) {
   if (!s || !inverse_dev || (!answers && n_unique)) return fail(C4_ERR_BAD_ARG, "null argument");
-  if (search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_step_gather: a search session (C4_FLAG_SEARCH) takes a device evaluator, not the callback mode's batches");
-  if (hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_step_gather: a hold session (C4_FLAG_HOLD) takes a device evaluator, not the callback mode's batches");
+  if (int rc = refuse_search_hold(s, "c4_session_step_gather", "takes a device evaluator, not the callback mode's batches")) return rc;
   if (!s->bound) return fail(C4_ERR_NOT_BOUND, "c4_session_step_gather: bind_io first");
   void *inv = nullptr, *ans = nullptr;
   {
@@ -2141,19 +1486,17 @@ int c4_session_step_head_out(c4_session* s, const void* hidden_policy_dev, const
                        (const uint4*)w_policy_dev, (const uint4*)w_value_dev, b_policy_dev, b_value_dev, s->p.slots, s->p.n_slots, features / 8,
                        policy_row_stride / 8, value_row_stride / 8, s->p);
   };
-  if (search_mode(s)) {
-    if (s->cfg.planes_dtype == 0)
-      return fail(C4_ERR_BAD_ARG, "c4_session_step_head_out: a search session's fused launch is built for bf16 planes (planes_dtype 1): call c4_head_out_bf16 and c4_session_step");
-    if (s->out_step_gpw == 4) launch(c4_out_step_kernel<uint16_t, 4, true>); else launch(c4_out_step_kernel<uint16_t, 8, true>);
-  } else if (hold_mode(s)) {
-    if (s->cfg.planes_dtype == 0)
-      return fail(C4_ERR_BAD_ARG, "c4_session_step_head_out: a hold session's fused launch is built for bf16 planes (planes_dtype 1): call c4_head_out_bf16 and c4_session_step");
-    if (s->out_step_gpw == 4) launch(c4_out_step_kernel<uint16_t, 4, false, true>); else launch(c4_out_step_kernel<uint16_t, 8, false, true>);
-  } else if (s->out_step_gpw == 4) {
-    if (s->cfg.planes_dtype == 0) launch(c4_out_step_kernel<float, 4>); else launch(c4_out_step_kernel<uint16_t, 4>);
-  } else {
-    if (s->cfg.planes_dtype == 0) launch(c4_out_step_kernel<float, 8>); else launch(c4_out_step_kernel<uint16_t, 8>);
-  }
+  // kGpw, mode -> kernel.  A search's and a hold session's fused launch exist for bf16 planes alone: refused here, not instantiated.
+  if (search_mode(s) && s->cfg.planes_dtype == 0)
+    return fail(C4_ERR_BAD_ARG, "c4_session_step_head_out: a search session's fused launch is built for bf16 planes (planes_dtype 1): call c4_head_out_bf16 and c4_session_step");
+  if (hold_mode(s) && s->cfg.planes_dtype == 0)
+    return fail(C4_ERR_BAD_ARG, "c4_session_step_head_out: a hold session's fused launch is built for bf16 planes (planes_dtype 1): call c4_head_out_bf16 and c4_session_step");
+  with_flag(s->out_step_gpw == 4, [&](auto four) {
+    constexpr uint32_t kGpw = decltype(four)::value ? 4 : 8;
+    if (search_mode(s)) launch(c4_out_step_kernel<uint16_t, kGpw, true>);
+    else if (hold_mode(s)) launch(c4_out_step_kernel<uint16_t, kGpw, false, true>);
+    else with_planes(s->cfg.planes_dtype, [&](auto planes) { launch(c4_out_step_kernel<decltype(planes), kGpw>); });
+  });
   HIP_TRY(hipGetLastError());
   return maybe_reclaim(s);
 }
@@ -2246,258 +1589,7 @@ int c4_session_progress(c4_session* s, uint64_t* games_done, uint64_t* games_sta
   return rc;
 }
 
-int c4_session_compact(c4_session* s, uint32_t multiple, uint32_t* n_active, uint32_t* n_slots_now) {
-  if (!s || !s->bound || !s->have_games) return fail(C4_ERR_BAD_ARG, "compact needs a bound session with games");
-  if (s->p.leaf_models) return fail(C4_ERR_BAD_ARG, "compaction does not move the per-slot model ids of multi-model sessions");
-  if (hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_compact: a hold session (C4_FLAG_HOLD) keeps request i on slot i: its per-slot arrays are indexed by it");
-  if (multiple == 0 || multiple % 8) return fail(C4_ERR_BAD_ARG, "multiple must be a positive multiple of 8");
-  C4_ON_DEVICE(s->cfg.device);
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  Globals g{};
-  HIP_TRY(hipMemcpy(&g, s->p.glob, sizeof g, hipMemcpyDeviceToHost));
-  if (n_slots_now) *n_slots_now = s->p.n_slots;
-  if (g.queue_head < s->n_games) {   // slots are still being refilled: nothing to gain
-    if (n_active) *n_active = s->p.n_slots;
-    return C4_OK;
-  }
-  if (!s->plan_dev) {
-    HIP_TRY(hipMalloc(&s->plan_dev, sizeof(CompactPlan)));
-    HIP_TRY(hipMalloc(&s->pairs_dev, (size_t)s->cfg.n_slots * sizeof(uint2)));
-  }
-  hipLaunchKernelGGL(k_compact_plan, dim3(1), dim3(1024), 0, s->stream, s->p.slots, s->p.n_slots, s->plan_dev, s->pairs_dev);
-  const uint32_t max_pairs = s->p.n_slots / 2 + 1;
-  if (s->cfg.planes_dtype == 0) hipLaunchKernelGGL(k_compact_move<float>, dim3(max_pairs), dim3(256), 0, s->stream, s->p, s->plan_dev, s->pairs_dev);
-  else hipLaunchKernelGGL(k_compact_move<uint16_t>, dim3(max_pairs), dim3(256), 0, s->stream, s->p, s->plan_dev, s->pairs_dev);
-  HIP_TRY(hipGetLastError());
-  CompactPlan plan{};
-  HIP_TRY(hipMemcpyAsync(&plan, s->plan_dev, sizeof plan, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  uint32_t want = ((plan.n_active + multiple - 1) / multiple) * multiple;
-  if (want < multiple) want = multiple;
-  if (want < s->p.n_slots) {
-    s->p.n_slots = want;
-    s->n_waves = (want + 64u / s->lanes_per_game - 1) / (64u / s->lanes_per_game);
-    s->p.n_waves = s->n_waves;
-    HIP_TRY(hipMemset(s->p.stamps, 0, (size_t)s->n_waves_cap * 4 * sizeof(unsigned long long)));   // the stamp stride changed
-  }
-  if (n_active) *n_active = plan.n_active;
-  if (n_slots_now) *n_slots_now = s->p.n_slots;
-  return C4_OK;
-}
-
-int c4_session_arena(c4_session* s, uint64_t* bytes, uint32_t* blocks_per_slot, uint32_t* reclaim_half_blocks) {
-  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
-  if (bytes) *bytes = s->arena_bytes;
-  if (blocks_per_slot) *blocks_per_slot = s->p.blocks_per_slot;
-  if (reclaim_half_blocks) *reclaim_half_blocks = s->p.half_blocks;
-  return C4_OK;
-}
-
-int c4_session_sample_counts(c4_session* s, uint32_t* counts_host, uint64_t n_games) {
-  if (!s || !counts_host) return fail(C4_ERR_BAD_ARG, "null argument");
-  if (n_games != s->n_games) return fail(C4_ERR_BAD_ARG, "n_games does not match set_games");
-  C4_ON_DEVICE(s->cfg.device);
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (n_games) HIP_TRY(hipMemcpy(counts_host, s->p.sample_counts, n_games * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return C4_OK;
-}
-
-int c4_session_drain_samples(c4_session* s, c4_sample_rec* dst_host, uint64_t cap, uint64_t* n_written) {
-  if (!s || !n_written) return fail(C4_ERR_BAD_ARG, "null argument");
-  if (!s->have_games) return fail(C4_ERR_NOT_BOUND, "set_games must precede drain_samples");
-  // The records are packed ON THE DEVICE (prefix sum + K6, as for the collective) and come back in ONE
-  // transfer straight into the caller's buffer: no host-side staging of the 43-record-per-game store.
-  uint64_t total = 0;
-  int rc = c4_session_pack_samples(s, nullptr, 0, &total);   // size query: offsets + total (synchronises the stream)
-  if (rc != C4_OK) return rc;
-  *n_written = total;
-  if (!dst_host || total == 0) return C4_OK;
-  if (cap < total) return fail(C4_ERR_BAD_ARG, "destination too small");
-  C4_ON_DEVICE(s->cfg.device);
-  c4_sample_rec* tmp = nullptr;
-  HIP_TRY(hipMalloc(&tmp, total * sizeof(c4_sample_rec)));
-  rc = c4_session_pack_samples(s, tmp, total, &total);
-  if (rc == C4_OK) {
-    const hipError_t e = hipMemcpy(dst_host, tmp, total * sizeof(c4_sample_rec), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(C4_ERR_HIP, std::string("drain_samples: copying the packed records: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(tmp);
-  return rc;
-}
-
-int c4_session_pack_samples(c4_session* s, c4_sample_rec* dst_dev, uint64_t cap, uint64_t* n_written) {
-  if (!s || !n_written) return fail(C4_ERR_BAD_ARG, "null argument");
-  if (!s->have_games) return fail(C4_ERR_NOT_BOUND, "set_games must precede pack_samples");
-  C4_ON_DEVICE(s->cfg.device);
-  // record offsets by a device prefix sum into the session's persistent buffer; only the total comes back
-  unsigned long long* total_dev = s->offsets_dev + (s->n_games ? s->n_games : 1);
-  hipLaunchKernelGGL(k_sample_offsets, dim3(1), dim3(1024), 0, s->stream, s->p.sample_counts, (unsigned long long)s->n_games,
-                     s->offsets_dev, total_dev);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->total_host, total_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  const uint64_t total = *s->total_host;
-  *n_written = total;
-  if (!dst_dev || total == 0) return C4_OK;  // size query
-  if (cap < total) return fail(C4_ERR_BAD_ARG, "destination too small");
-  hipLaunchKernelGGL(k_pack_samples, dim3((unsigned)s->n_games), dim3(64), 0, s->stream, s->p.samples, s->p.sample_counts,
-                     s->offsets_dev, s->n_games, dst_dev);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return C4_OK;
-}
-
-// diagnostic builds only: raw phase stamps [n_waves][16] of the last launch (zeros otherwise)
-int c4_session_debug_phase_stamps(c4_session* s, uint64_t* out_host, uint64_t cap_words, uint64_t* n_words) {
-  if (!s || !n_words) return fail(C4_ERR_BAD_ARG, "null argument");
-  *n_words = (uint64_t)s->n_waves * 16;
-  if (!out_host) return C4_OK;
-  if (cap_words < *n_words) return fail(C4_ERR_BAD_ARG, "destination too small");
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  HIP_TRY(hipMemcpy(out_host, s->p.phase, *n_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return C4_OK;
-}
-
-int c4_session_sample_store(c4_session* s, const c4_sample_rec** recs_dev, const uint32_t** counts_dev, uint64_t* n_games) {
-  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
-  if (recs_dev) *recs_dev = s->p.samples;
-  if (counts_dev) *counts_dev = s->p.sample_counts;
-  if (n_games) *n_games = s->n_games;
-  return C4_OK;
-}
-
-int c4_session_root_stats(c4_session* s, uint32_t slot, float policy[7], float* q_penalty, float* q_no_penalty,
-                          uint64_t* visit_count, uint64_t* root_mask, uint64_t* root_value) {
-  if (!s || slot >= s->cfg.n_slots) return fail(C4_ERR_BAD_ARG, "bad slot");
-  C4_ON_DEVICE(s->cfg.device);
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  Slot st;
-  HIP_TRY(hipMemcpy(&st, s->p.slots + slot, sizeof st, hipMemcpyDeviceToHost));
-  const size_t base = (size_t)slot * s->cfg.blocks_per_slot;
-  Block rb;
-  HIP_TRY(hipMemcpy(&rb, s->p.blocks + base + (st.root_ref >> 3), sizeof rb, hipMemcpyDeviceToHost));
-  const Entry& re = rb.e[st.root_ref & 7];
-  // mcts.rs:359-367: q_sum / (visit_count as f32 + 1.0)
-  const float nf = (float)re.n + 1.0f;
-  if (q_penalty) *q_penalty = re.q_pen / nf;
-  if (q_no_penalty) *q_no_penalty = re.q_nopen / nf;
-  if (visit_count) *visit_count = re.n;
-  if (root_mask) *root_mask = st.root_mask;
-  if (root_value) *root_value = st.root_value;
-  if (policy) {
-    // mcts.rs:396-412
-    float cnt[7] = {0, 0, 0, 0, 0, 0, 0}, sum = 0.0f;
-    const uint32_t root_block = st.arena >> 16;
-    if (root_block) {
-      Block cb;
-      HIP_TRY(hipMemcpy(&cb, s->p.blocks + base + root_block, sizeof cb, hipMemcpyDeviceToHost));
-      for (int c = 0; c < 7; c++) cnt[c] = (float)cb.e[c].n;
-    }
-    for (int c = 0; c < 7; c++) sum = sum + cnt[c];
-    for (int c = 0; c < 7; c++) policy[c] = (sum == 0.0f) ? (1.0f / 7.0f) : cnt[c] / sum;
-  }
-  return C4_OK;
-}
-
-int c4_session_leaf_keys(c4_session* s, int64_t* keys_dev) {
-  if (!s || !keys_dev) return fail(C4_ERR_BAD_ARG, "null argument");
-  C4_ON_DEVICE(s->cfg.device);
-  hipLaunchKernelGGL(k_leaf_keys, dim3((s->cfg.n_slots + 255) / 256), dim3(256), 0, s->stream, s->p.slots, s->cfg.n_slots, (long long*)keys_dev);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-// A pointer kernels of device `device` may use for `ptr`: device memory of that device as it is, pinned host
-// memory through its device mapping; anything else (pageable host memory, another device) is refused here,
-// where the message can say so, instead of faulting inside a kernel.
-static int device_view(const void* ptr, int device, const char* what, void** out) {
-  hipPointerAttribute_t attr{};
-  const hipError_t e = hipPointerGetAttributes(&attr, ptr);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(C4_ERR_BAD_ARG, std::string(what) + " is neither device memory nor pinned host memory (" + hipGetErrorString(e) + ")");
-  }
-  if (attr.type == hipMemoryTypeHost) {
-    if (!attr.devicePointer) return fail(C4_ERR_BAD_ARG, std::string(what) + ": pinned host memory without a device mapping");
-    *out = attr.devicePointer;
-    return C4_OK;
-  }
-  if (attr.type == hipMemoryTypeManaged || (attr.type == hipMemoryTypeDevice && attr.device == device)) { *out = const_cast<void*>(ptr); return C4_OK; }
-  return fail(C4_ERR_BAD_ARG, std::string(what) + " is neither memory of device " + std::to_string(device) + " nor pinned host memory");
-}
-
-int c4_session_unique_leaves(c4_session* s, uint32_t* inverse_dev, float* rows_out, uint64_t* models_out, uint32_t* n_unique_out) {
-  if (!s || !inverse_dev || !rows_out || !n_unique_out) return fail(C4_ERR_BAD_ARG, "null argument");
-  if (search_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: a search session (C4_FLAG_SEARCH) takes a device evaluator, not the callback mode's batches");
-  if (hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: a hold session (C4_FLAG_HOLD) takes a device evaluator, not the callback mode's batches");
-  if (!s->bound || !s->have_games) return fail(C4_ERR_BAD_ARG, "c4_session_unique_leaves: bind_io and set_games first");
-  C4_ON_DEVICE(s->cfg.device);
-  const uint32_t n = s->cfg.n_slots;
-  void *inv = nullptr, *rows = nullptr, *models = nullptr, *count = nullptr;
-  if (int rc = device_view(inverse_dev, s->cfg.device, "c4_session_unique_leaves: inverse_dev", &inv)) return rc;
-  if (int rc = device_view(rows_out, s->cfg.device, "c4_session_unique_leaves: rows_out", &rows)) return rc;
-  if (models_out) if (int rc = device_view(models_out, s->cfg.device, "c4_session_unique_leaves: models_out", &models)) return rc;
-  if (int rc = device_view(n_unique_out, s->cfg.device, "c4_session_unique_leaves: n_unique_out", &count)) return rc;
-  if (!s->uniq_tab) {
-    uint32_t cells = 64;
-    while (cells < 2 * n) cells <<= 1;                             // at most half full: short probe runs
-    // all four or none: the session's fields are set only when every allocation succeeded (a half-made table with
-    // mask 0 would send the next call's kernels through null pointers)
-    uint32_t *tab = nullptr, *cell = nullptr, *row = nullptr, *cnt = nullptr;
-    hipError_t e = hipMalloc(&tab, (size_t)cells * 4);
-    if (e == hipSuccess) e = hipMalloc(&cell, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc(&row, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc(&cnt, 4);
-    if (e == hipSuccess) e = hipMemsetAsync(tab, 0xFF, (size_t)cells * 4, s->stream);   // empty; k_unique_emit keeps it so
-    if (e != hipSuccess) {
-      (void)hipFree(tab); (void)hipFree(cell); (void)hipFree(row); (void)hipFree(cnt);
-      return fail(C4_ERR_HIP, std::string("c4_session_unique_leaves: ") + hipGetErrorString(e));
-    }
-    s->uniq_tab = tab; s->uniq_cell = cell; s->uniq_row = row; s->uniq_count = cnt;
-    s->uniq_tab_mask = cells - 1;
-  }
-  hipLaunchKernelGGL(k_unique_insert, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->p.slots, s->p.leaf_models, n, s->uniq_tab,
-                     s->uniq_tab_mask, s->uniq_cell);
-  hipLaunchKernelGGL(k_unique_rank, dim3(1), dim3(1024), 0, s->stream, s->uniq_tab, s->uniq_cell, n, s->uniq_row, (uint32_t*)inv,
-                     s->uniq_count, (uint32_t*)count);
-  hipLaunchKernelGGL(k_unique_emit, dim3((n + 3) / 4), dim3(256), 0, s->stream, s->p.slots, s->p.leaf_models, n, s->uniq_tab,
-                     s->uniq_cell, s->uniq_row, (float*)rows, (uint64_t*)models);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-int c4_session_scatter_outputs(c4_session* s, const uint32_t* inverse_dev, const float* answers, uint32_t n_unique) {
-  if (!s || !inverse_dev || (!answers && n_unique)) return fail(C4_ERR_BAD_ARG, "null argument");
-  if (!s->bound) return fail(C4_ERR_BAD_ARG, "c4_session_scatter_outputs: bind_io first");
-  if (n_unique == 0) return C4_OK;
-  C4_ON_DEVICE(s->cfg.device);
-  void *inv = nullptr, *ans = nullptr;
-  if (int rc = device_view(inverse_dev, s->cfg.device, "c4_session_scatter_outputs: inverse_dev", &inv)) return rc;
-  if (int rc = device_view(answers, s->cfg.device, "c4_session_scatter_outputs: answers", &ans)) return rc;
-  const uint32_t n = s->cfg.n_slots;
-  hipLaunchKernelGGL(k_unique_scatter, dim3((n * 9 + 255) / 256), dim3(256), 0, s->stream, (const uint32_t*)inv, (const float*)ans, n,
-                     n_unique, const_cast<float*>(s->p.logprobs), const_cast<float*>(s->p.q));
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-int c4_session_leaves(c4_session* s, uint64_t* masks_host, uint64_t* values_host, uint32_t* status_host,
-                      uint32_t* ordinals_host) {
-  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
-  C4_ON_DEVICE(s->cfg.device);
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  std::vector<Slot> h(s->cfg.n_slots);
-  HIP_TRY(hipMemcpy(h.data(), s->p.slots, h.size() * sizeof(Slot), hipMemcpyDeviceToHost));
-  for (uint32_t g = 0; g < s->cfg.n_slots; g++) {
-    if (masks_host) masks_host[g] = h[g].leaf_mask;
-    if (values_host) values_host[g] = h[g].leaf_value;
-    if (status_host) status_host[g] = h[g].state & 0xFFu;
-    if (ordinals_host) ordinals_host[g] = h[g].ordinal;
-  }
-  return C4_OK;
-}
-
-// ---- hold sessions (C4_FLAG_HOLD): target, moves from outside, snapshot, probe ----
+// ---- hold sessions (C4_FLAG_HOLD): target, moves from outside (snapshot and probe: c4_session_readout.hip) ----
 int c4_session_set_iterations(c4_session* s, uint32_t n_mcts_iterations) {
   if (!s) return fail(C4_ERR_BAD_ARG, "null session");
   if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_set_iterations: not a hold session (C4_FLAG_HOLD); a session of games or searches keeps the n_mcts_iterations it was created with");
@@ -2505,23 +1597,6 @@ int c4_session_set_iterations(c4_session* s, uint32_t n_mcts_iterations) {
     return fail(C4_ERR_BAD_ARG, "c4_session_set_iterations: the target must be between 1 and the n_mcts_iterations the session was created with (" +
                                     std::to_string(s->cfg.n_mcts_iterations) + "), which sizes its tree arena and its table of logarithms");
   s->p.n_iter = n_mcts_iterations;   // a kernel argument of every later launch: stream-ordered by construction
-  return C4_OK;
-}
-
-// One per-slot array of c4_session_hold_resume as the kernel may use it: device memory and pinned host memory through
-// device_view; pageable host memory (what HIP does not know) through the session's staging buffer `stage` (copied in now when
-// `copy_in`).  *staged tells the caller which.
-static int hold_array(c4_session* s, const void* ptr, void** stage, bool copy_in, const char* what, void** out, bool* staged) {
-  const size_t bytes = (size_t)s->cfg.n_slots * 4;
-  *staged = false;
-  hipPointerAttribute_t attr{};
-  const hipError_t e = hipPointerGetAttributes(&attr, ptr);
-  if (e == hipSuccess && attr.type != hipMemoryTypeUnregistered) return device_view(ptr, s->cfg.device, what, out);
-  if (e != hipSuccess) (void)hipGetLastError();
-  if (!*stage) HIP_TRY(hipMalloc(stage, bytes));
-  if (copy_in) HIP_TRY(hipMemcpyAsync(*stage, ptr, bytes, hipMemcpyHostToDevice, s->stream));
-  *out = *stage;
-  *staged = true;
   return C4_OK;
 }
 
@@ -2542,109 +1617,12 @@ int c4_session_hold_resume(c4_session* s, const int32_t* cols, const float* temp
   return C4_OK;
 }
 
-int c4_session_snapshot(c4_session* s, c4_sample_rec* dst_host, uint32_t* visits_host, uint32_t* status_host, uint64_t cap) {
-  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
-  if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_snapshot: not a hold session (C4_FLAG_HOLD)");
-  if (!s->have_games) return fail(C4_ERR_NOT_BOUND, "set_games must precede c4_session_snapshot");
-  const size_t n = s->cfg.n_slots;
-  if (cap < n) return fail(C4_ERR_BAD_ARG, "c4_session_snapshot: the arrays hold one entry per slot (" + std::to_string(n) + ")");
-  C4_ON_DEVICE(s->cfg.device);
-  const size_t bytes = n * (sizeof(c4_sample_rec) + 8);   // [n] records, [n] visit counts, [n] status words
-  if (!s->snap_dev) {
-    HIP_TRY(hipMalloc(&s->snap_dev, bytes));
-    HIP_TRY(hipHostMalloc(&s->snap_host, bytes));
-  }
-  c4_sample_rec* recs = (c4_sample_rec*)s->snap_dev;
-  uint32_t* visits = (uint32_t*)(s->snap_dev + n * sizeof(c4_sample_rec));
-  hipLaunchKernelGGL(k_hold_snapshot, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, s->stream, s->p, recs, visits, visits + n);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->snap_host, s->snap_dev, bytes, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (dst_host) memcpy(dst_host, s->snap_host, n * sizeof(c4_sample_rec));
-  if (visits_host) memcpy(visits_host, s->snap_host + n * sizeof(c4_sample_rec), n * 4);
-  if (status_host) memcpy(status_host, s->snap_host + n * sizeof(c4_sample_rec) + n * 4, n * 4);
-  return C4_OK;
-}
-
-int c4_session_hold_poll(c4_session* s, uint32_t* n_active, uint32_t* max_need, uint32_t* error) {
-  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
-  if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_hold_poll: not a hold session (C4_FLAG_HOLD)");
-  const int rc = c4_session_poll(s, nullptr, error);
-  if (rc != C4_OK) return rc;
-  if (n_active) *n_active = s->hold_probe_valid ? s->hold_probe_active : C4_HOLD_POLL_UNKNOWN;
-  if (max_need) *max_need = s->hold_probe_valid ? s->hold_probe_need : C4_HOLD_POLL_UNKNOWN;
-  return C4_OK;
-}
-
-// ---- element-wise entry points ----
-// They run on the device their stream belongs to (the caller's current device for the null stream) and
-// leave the caller's current device as they found it, like the session entry points.
-static inline dim3 grid_for(uint64_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
-#define C4_ON_STREAM_DEVICE(stream) C4_ON_DEVICE(c4host::stream_device((hipStream_t)(stream)))
-
-int c4_pos_ops(const uint64_t* mask_dev, const uint64_t* value_dev, const int32_t* col_dev, uint64_t n, float c_ply_penalty,
-               uint64_t* out_mask_dev, uint64_t* out_value_dev, uint32_t* out_legal_dev, uint32_t* out_terminal_dev,
-               float* out_q_dev, void* stream) {
-  if (n == 0) return C4_OK;
-  C4_ON_STREAM_DEVICE(stream);
-  hipLaunchKernelGGL(k_pos_ops, grid_for(n), dim3(256), 0, (hipStream_t)stream, mask_dev, value_dev, col_dev, n, c_ply_penalty,
-                     out_mask_dev, out_value_dev, out_legal_dev, out_terminal_dev, out_q_dev);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-int c4_encode_planes(const uint64_t* mask_dev, const uint64_t* value_dev, uint64_t n, uint32_t planes_dtype, void* planes_dev, void* stream) {
-  if (n == 0) return C4_OK;
-  C4_ON_STREAM_DEVICE(stream);
-  if (planes_dtype == 0)
-    hipLaunchKernelGGL(k_encode<float>, grid_for(n * C4_PLANES_LEN), dim3(256), 0, (hipStream_t)stream, mask_dev, value_dev, n, planes_dev);
-  else if (planes_dtype == 1)
-    hipLaunchKernelGGL(k_encode<uint16_t>, grid_for(n * C4_PLANES_LEN), dim3(256), 0, (hipStream_t)stream, mask_dev, value_dev, n, planes_dev);
-  else
-    return fail(C4_ERR_BAD_ARG, "planes_dtype must be 0 or 1");
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-int c4_expf_logf(const float* x_dev, uint64_t n, int which, float* y_dev, void* stream) {
-  if (n == 0) return C4_OK;
-  C4_ON_STREAM_DEVICE(stream);
-  hipLaunchKernelGGL(k_expf_logf, grid_for(n), dim3(256), 0, (hipStream_t)stream, x_dev, n, which, y_dev);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-int c4_softmax7(const float* logits_dev, const uint32_t* legal_dev, uint64_t n, float* out_dev, uint32_t* out_err_dev, void* stream) {
-  if (n == 0) return C4_OK;
-  C4_ON_STREAM_DEVICE(stream);
-  hipLaunchKernelGGL(k_softmax7, grid_for(n), dim3(256), 0, (hipStream_t)stream, logits_dev, legal_dev, n, out_dev, out_err_dev);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-int c4_apply_temperature(const float* policy_dev, const float* temperature_dev, uint64_t n, float* out_dev, void* stream) {
-  if (n == 0) return C4_OK;
-  C4_ON_STREAM_DEVICE(stream);
-  hipLaunchKernelGGL(k_temperature, grid_for(n), dim3(256), 0, (hipStream_t)stream, policy_dev, temperature_dev, n, out_dev);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
+// (the parity tests' entry point of k_dirichlet, see there)
 int c4_dirichlet(const uint64_t* game_id_dev, const uint32_t* n_moves_dev, const uint32_t* legal_dev, float alpha, uint64_t n,
                  float* eta_dev, void* stream) {
   if (n == 0) return C4_OK;
   C4_ON_STREAM_DEVICE(stream);
   hipLaunchKernelGGL(k_dirichlet, grid_for(n, 64), dim3(64), 0, (hipStream_t)stream, game_id_dev, n_moves_dev, legal_dev, alpha, n, eta_dev);
-  HIP_TRY(hipGetLastError());
-  return C4_OK;
-}
-
-int c4_sample_move(const uint64_t* game_id_dev, const uint32_t* n_moves_dev, const float* policy_dev, const float* temperature_dev,
-                   uint64_t n, int32_t* out_col_dev, uint32_t* out_u32_dev, void* stream) {
-  if (n == 0) return C4_OK;
-  C4_ON_STREAM_DEVICE(stream);
-  hipLaunchKernelGGL(k_sample_move, grid_for(n), dim3(256), 0, (hipStream_t)stream, game_id_dev, n_moves_dev, policy_dev,
-                     temperature_dev, n, out_col_dev, out_u32_dev);
   HIP_TRY(hipGetLastError());
   return C4_OK;
 }

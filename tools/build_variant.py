@@ -21,13 +21,24 @@ def main():
     rev = sys.argv[2] if len(sys.argv) > 2 else "HEAD"
     defines = [a for a in sys.argv[3:] if a.startswith("-D")]
     out = os.path.join(ROOT, "c4a0_amd", f"libc4a0_hip_{name}.so")
+    in_rev = set()
+    if rev != "WORK":   # an unknown revision is an error here, not a build without sources
+        r = subprocess.run(["git", "rev-parse", "--verify", "--quiet", rev + "^{commit}"], cwd=ROOT, capture_output=True, text=True)
+        if r.returncode:
+            sys.exit(f"build_variant: {rev!r} is not a revision of this repository")
+        in_rev = set(subprocess.run(["git", "ls-tree", "-r", "--name-only", rev], cwd=ROOT, capture_output=True, text=True, check=True).stdout.split("\n"))
     with tempfile.TemporaryDirectory() as td:
         os.makedirs(os.path.join(td, "c4a0_amd", "csrc"))
         os.makedirs(os.path.join(td, "include"))
         srcs = []
         for d in B.DEPS:
             rel = os.path.relpath(d, ROOT)
-            data = open(d, "rb").read() if rev == "WORK" else subprocess.run(["git", "show", f"{rev}:{rel}"], cwd=ROOT, capture_output=True, check=True).stdout
+            if rev == "WORK":
+                data = open(d, "rb").read()
+            elif rel not in in_rev:   # a file the revision does not have yet (the session was one file before it was split by concern)
+                continue
+            else:
+                data = subprocess.run(["git", "show", f"{rev}:{rel}"], cwd=ROOT, capture_output=True, check=True).stdout
             dst = os.path.join(td, rel)
             with open(dst, "wb") as f:
                 f.write(data)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The FETCH_SIZE / WRITE_SIZE passes of tools/profile/run_r06.sh alone (each --pmc pass its own run, --kernel-trace only), re-run whenever
-# c4_session.hip or c4_device.hpp changes: profiles/step_kernel_traffic.json records the hash of those two files, and bench.py says whether
+# c4_session.hip, c4_device.hpp or c4_tree.hpp changes: profiles/step_kernel_traffic.json records the hash of the first two files, and bench.py says whether
 # the traffic figure was collected on the step kernel it is running.   gpurun -- 'bash tools/profile/run_r06_traffic.sh'
 O=gpurun_out/r06t; mkdir -p $O; export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
