@@ -27,7 +27,9 @@ HOLD_MOVE_NONE, HOLD_MOVE_SAMPLE = -1, -2   # c4_session_hold_resume: a slot's m
 HOLD_OK, HOLD_REFUSED_TERMINAL, HOLD_REFUSED_COLUMN, HOLD_REFUSED_UNSEARCHED, HOLD_REFUSED_SAMPLE, HOLD_NO_GAME = range(6)   # ... and its result
 HOLD_POLL_UNKNOWN = 0xFFFFFFFF
 MAX_SAMPLES_PER_GAME = 43
-ABI_VERSION = 13   # include/c4a0_hip.h C4_ABI_VERSION: the signatures below are that version's
+ROUTE_MAX_MODELS = 32     # include/c4a0_hip.h C4_ROUTE_MAX_MODELS: models one routed batch (c4_session_route_leaves) may hold
+GROUPED_ROW_ALIGN = 128   # include/c4a0_hip.h C4_GROUPED_ROW_ALIGN == c4_grouped_row_align(): segments of a grouped batch are multiples of it
+ABI_VERSION = 14   # include/c4a0_hip.h C4_ABI_VERSION: the signatures below are that version's
 STRUCT_LAYOUT_SINCE = 7   # the ABI version that last changed a structure's layout (c4_config.reclaim_period, c4_counters.reclaim_*)
 
 
@@ -132,6 +134,7 @@ SIGNATURES = {
     "c4_session_unique_leaves": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "c4_session_scatter_outputs": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "c4_session_step_gather": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
+    "c4_session_route_leaves": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
     "c4_session_set_iterations": (C.c_int, [_vp, C.c_uint32]),
     "c4_session_hold_resume": (C.c_int, [_vp, _vp, _vp, _vp]),
     "c4_session_snapshot": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64]),
@@ -147,6 +150,10 @@ SIGNATURES = {
     "c4_linear_bf16_tile_map": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),
     "c4_planes_from_f32": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     "c4_head_out_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "c4_grouped_row_align": (C.c_int, []),
+    "c4_conv_tower_bf16_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "c4_linear_bf16_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "c4_head_out_bf16_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "c4_dirichlet": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint64, _vp, _vp]),
     "c4_sample_move": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "c4_conv_tower_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),

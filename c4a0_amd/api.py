@@ -182,6 +182,55 @@ class _MultiModelEvaluator:
         return lp_out, q_out
 
 
+class _GroupedModelEvaluator:
+    """Device-mode tournaments from a HIP graph: what _MultiModelEvaluator does with a sort, two host reads and one eager chain per
+    model is here pure device work of a fixed shape.  c4_session_route_leaves groups the resident games' leaves by the model that
+    must answer them (segment bounds in device memory only), the grouped bf16 chain (c4a0_amd.nn.GroupedNets) evaluates every
+    segment with its model's weights in one launch per layer, and every slot takes its answer from its row.  A row's outputs are
+    the bits its model's InferenceNet computes for that position, so the records are those of the eager path.
+
+    __call__ is the evaluate() form (warm-up of capture_steps, observers): the answers go to the bound logprobs / q tensors
+    (c4_session_scatter_outputs).  round() hands them over inside the step's launch (c4_session_step_gather); DeviceSession.round
+    dispatches to it."""
+    graph_safe = True        # pure device work on persistent tensors, no host synchronisation
+    batch_invariant = True   # every kernel of the chain computes a row from that row and its model's weights alone
+    gather_step = True       # round(): scatter + step as one launch (False: A/B)
+
+    def __init__(self, session: DeviceSession, grouped):
+        self.s, self.g = session, grouped
+        if session.planes.dtype != torch.bfloat16:
+            raise ValueError("the grouped chain reads bf16 planes")
+        self.models = session.bind_leaf_models()
+        self.align = grouped.row_align
+        from .session import route_rows_cap
+        self.rows_cap = route_rows_cap(session.n_slots, grouped.n_models, self.align)
+        dev = session.device
+        with torch.cuda.device(dev):
+            self.buf = grouped.buffers(self.rows_cap)
+            self.inverse = torch.zeros(session.n_slots, dtype=torch.int32, device=dev)
+            self.seg_start = torch.zeros(grouped.n_models + 1, dtype=torch.int32, device=dev)
+            self.n_unrouted = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _answers(self):
+        self.s.route_leaves(self.g.model_ids, self.align, self.buf["planes"], self.inverse, self.seg_start, self.n_unrouted)
+        return self.g.forward(self.buf, self.seg_start)
+
+    def __call__(self, _planes=None, out_logprobs=None, out_q=None):
+        s = self.s
+        ans = self._answers()
+        check(s.L.c4_session_scatter_outputs(s._h, self.inverse.data_ptr(), ans.data_ptr(), self.rows_cap))
+        return s.logprobs, s.q
+
+    def round(self):
+        s = self.s
+        if not self.gather_step:
+            self()
+            s.step()
+            return
+        ans = self._answers()
+        check(s.L.c4_session_step_gather(s._h, self.inverse.data_ptr(), ans.data_ptr(), self.rows_cap))
+
+
 def _ids_of(reqs) -> np.ndarray:
     """uint64[n, 3] (game_id, player0_id, player1_id) of the requests: the one pass over the caller's objects."""
     try:
@@ -230,7 +279,12 @@ def play_games(reqs: Sequence[GameMetadata], max_nn_batch_size: int, n_mcts_iter
     hand-over in C++ -- as the reference's `self_play()` is compiled code, self_play.rs:39-129); every other evaluator (numpy
     callbacks, arbitrary device callables, tournaments, subclasses that override `forward`) is driven by the Python loop of
     c4a0_amd/session.py, which implements the same schedule.  None = that choice; "python" forces the Python loop, "native"
-    insists on the library's (TypeError if the evaluator is not one it can run).  Same records either way."""
+    insists on the library's (TypeError if the evaluator is not one it can run).  Same records either way.
+
+    Tournaments (evaluator={model_id: evaluator, ...}): unmodified bf16 `InferenceNet`s of one architecture are stacked
+    (`c4a0_amd.nn.GroupedNets`) and the job is replayed from a HIP graph -- the leaves routed by model on the device, one grouped launch
+    per layer, no host synchronisation per round; anything else is evaluated per model with a gathered batch each round.
+    stats["multi_model"] is "grouped" or "eager", stats["multi_model_reason"] why not grouped.  Same records either way."""
     reqs = list(reqs)
     if py_eval_pos_cb is not None and evaluator is None and getattr(py_eval_pos_cb, "device_evaluator", None) is not None:
         evaluator, py_eval_pos_cb = py_eval_pos_cb.device_evaluator, None
@@ -343,6 +397,22 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
         if host_loop == "native":
             raise TypeError(f"host_loop='native': {why}")
     multi = evaluator is not None and isinstance(evaluator, dict)
+    # Tournaments: bf16 networks of one architecture on the hand-written kernels are stacked (nn.GroupedNets) and the job is replayed
+    # from a HIP graph on one session (_GroupedModelEvaluator); anything else keeps the eager per-model path (_MultiModelEvaluator)
+    grouped, grouped_why = None, None
+    if multi:
+        from .nn import GroupedNets
+        grouped_why = GroupedNets.refusal(evaluator)
+        if grouped_why is None and planes_dtype not in (None, torch.bfloat16):
+            grouped_why = "planes_dtype must be bfloat16"
+        if grouped_why is None and concurrent_sessions not in (None, 0, 1):
+            grouped_why = "one session plays a tournament"
+        if grouped_why is None and device is not None and torch.device(device) != next(iter(evaluator.values())).device and \
+                not (torch.device(device).index is None and torch.device(device).type == "cuda"):
+            grouped_why = "device= names another device than the evaluators'"
+        if grouped_why is None:
+            grouped = GroupedNets(evaluator)
+            device, planes_dtype = grouped.device, torch.bfloat16
     if planes_dtype is None:   # hand a bf16 network bf16 planes (0/1 are exact): no conversion kernel per step
         planes_dtype = torch.bfloat16 if getattr(evaluator, "dtype", None) == torch.bfloat16 else torch.float32
     graph_safe = evaluator is not None and not multi and getattr(evaluator, "graph_safe", False)
@@ -369,7 +439,7 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
     # for two paired sessions, short ones from the first narrowing of the tail on, where the graph is captured again anyway
     # (session._run_pair).  The reference's default job (1 700 games, n = 1 400: 37 000 rounds, one session) replays 32.
     est_rounds = -(-len(reqs) // max(1, n_slots)) * (1 if search else 15) * max(1, int(n_mcts_iterations))   # (a search: n simulations, no moves)
-    if not graph_safe:
+    if not graph_safe and grouped is None:
         steps_per_graph = tail_steps_per_graph = 0
     elif parts == 2:
         steps_per_graph = 64 if est_rounds >= 4000 else (32 if est_rounds >= 1500 else 8)
@@ -402,6 +472,9 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
         elif evaluator is None:
             ev = _CallbackEvaluator(sessions[0], py_eval_pos_cb, max_nn_batch_size, reqs[:, 1], reqs[:, 2])
             steps = sessions[0].run(ev, poll_every=4, phases=phases)   # the completion probe every 4th step: at most 3 idle steps at the very end
+        elif grouped is not None:   # (chosen as for a single graph-safe evaluator on one session)
+            steps = sessions[0].run(_GroupedModelEvaluator(sessions[0], grouped), steps_per_graph=steps_per_graph, phases=phases,
+                                    tail_steps_per_graph=tail_steps_per_graph)
         elif multi:
             steps = sessions[0].run(_MultiModelEvaluator(sessions[0], evaluator), phases=phases)
         else:
@@ -440,6 +513,10 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
             stats["rows_at_end"] = sum(s.rows for s in sessions)
             stats["concurrent_sessions"] = parts
             stats["host_loop"] = "python"
+            if multi:   # which path the tournament took, and why not the grouped one
+                stats["multi_model"] = "grouped" if grouped is not None else "eager"
+                if grouped is None:
+                    stats["multi_model_reason"] = grouped_why
             if evaluator is None:
                 stats["nn_positions"] = ev.nn_positions
     finally:

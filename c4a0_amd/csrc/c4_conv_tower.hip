@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "../../include/c4a0_hip.h"
+#include "c4_grouped.hpp"
 #include "c4_head_out.hpp"
 #include "c4_host.hpp"
 #include "c4_timeline.hpp"
@@ -478,10 +479,23 @@ __device__ __forceinline__ void dma_weights(const void* w, uint32_t bytes, uint4
 // ST (C = 64): the residual layers run as tower_layer_stream (weights streamed through a ring, k-steps outside).
 // KD (ST only): k-steps of weights in flight in the register ring.
 // RG (ST, MS = 2, 8 wavefronts): the weights through the workgroup's LDS ring (RingFeed) instead of every wavefront's own global loads.
-template <int C, int NB, int NT, int MS, bool ST = false, int KD = 3, bool RG = false>
+// GA: nothing (the kernel of c4_conv_tower_bf16: the arguments and the code it has always had), or the grouped form's two further
+// arguments (const uint32_t* seg_start, uint32_t n_models: 15 dwords, still all preloaded) -- c4_conv_tower_bf16_grouped: a workgroup
+// finds the model whose row segment holds its first board, moves the three weight operands to that model's set (the sets are
+// stacked, one after the other) and runs the same code; past the last segment it writes nothing.
+template <int C, int NB, int NT, int MS, bool ST = false, int KD = 3, bool RG = false, typename... GA>
 __global__ __launch_bounds__(NT) void c4_conv_tower_kernel(const uint16_t* __restrict__ a_planes, const bf16x8* __restrict__ a_w0, const bf16x8* __restrict__ a_w,
-                                                             const float* __restrict__ a_bias, uint16_t* __restrict__ a_out, uint32_t a_n_boards, uint32_t a_n_blocks) {
+                                                             const float* __restrict__ a_bias, uint16_t* __restrict__ a_out, uint32_t a_n_boards, uint32_t a_n_blocks,
+                                                             GA... a_group) {
   // flat scalar arguments (12 dwords): preloaded into SGPRs at wavefront launch (build.py: -amdgpu-kernarg-preload-count)
+  if constexpr (sizeof...(GA) != 0) {
+    const c4grp::Segments seg{a_group...};
+    const int model = seg.model_of(blockIdx.x * NB);
+    if (model < 0) return;                           // (the whole workgroup: no barrier has been met)
+    a_w0 += (size_t)model * (3 * (C / 16) * 64);
+    a_w += (size_t)model * ((size_t)2 * a_n_blocks * 9 * (C / 16) * (C / 32) * 64);
+    a_bias += (size_t)model * ((1 + 2 * a_n_blocks) * C);
+  }
   const TowerParams p{a_planes, a_w0, a_w, a_bias, a_out, a_n_boards, a_n_blocks};
   C4_TL_BEGIN();
 #ifdef C4_PHASE_STAMPS
@@ -759,14 +773,14 @@ __global__ __launch_bounds__(NT) void c4_conv_tower_kernel(const uint16_t* __res
   C4_TL_END(1, p.out);
 }
 
-template <int C, int NB, int NT, int MS, bool ST = false, int KD = 3, bool RG = false>
-int launch_tower(const TowerParams& p, uint32_t n_boards, hipStream_t stream, int device) {
+template <int C, int NB, int NT, int MS, bool ST = false, int KD = 3, bool RG = false, typename... GA>
+int launch_tower(const TowerParams& p, uint32_t n_boards, hipStream_t stream, int device, GA... group) {
   // + the wavefront pairs' hand-over counters; RG: + the weight ring (4 stages) and the residual layers' biases
   const int kLds = Geo<C, NB>::kLdsBytes + (ST ? 64 : 0) + (RG ? 4 * RingFeed<C>::kStageSlots * 16 + 2 * (int)p.n_blocks * C * 4 : 0);
-  auto k = c4_conv_tower_kernel<C, NB, NT, MS, ST, KD, RG>;
+  auto k = c4_conv_tower_kernel<C, NB, NT, MS, ST, KD, RG, GA...>;
   hipError_t e = c4host::opt_in_lds((const void*)k, RG ? 160 * 1024 : kLds, device);   // (RG: the size depends on the number of layers; the opt-in is made once per kernel)
   if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_conv_tower_bf16: LDS opt-in (") + std::to_string(kLds) + " bytes) on device " + std::to_string(device) + ": " + hipGetErrorString(e));
-  k<<<dim3((n_boards + NB - 1) / NB), dim3(NT), kLds, stream>>>(p.planes, p.w0, p.w, p.bias, p.out, p.n_boards, p.n_blocks);
+  k<<<dim3((n_boards + NB - 1) / NB), dim3(NT), kLds, stream>>>(p.planes, p.w0, p.w, p.bias, p.out, p.n_boards, p.n_blocks, group...);
   e = hipGetLastError();
   if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_conv_tower_bf16 launch: ") + hipGetErrorString(e));
   return C4_OK;
@@ -854,6 +868,27 @@ int c4_conv_tower_bf16(const void* planes_dev, const void* w0_dev, const void* w
   if (channels == 64 && config == 4 && Geo<64, 8>::kLdsBytes + 64 + 4 * RingFeed<64>::kStageSlots * 16 + 2 * (int)n_blocks * 64 * 4 <= 160 * 1024)
     return launch_tower<64, 8, 512, 2, true, 2, true>(p, n_boards, (hipStream_t)stream, device);
   return launch_tower<64, 8, 512, 2, true>(p, n_boards, (hipStream_t)stream, device);   // 8 wavefronts: pairs split the output channels; weights streamed
+}
+
+int c4_grouped_row_align(void) { return C4_GROUPED_ROW_ALIGN; }
+
+// c4_conv_tower_bf16 for a batch whose rows are grouped by model (c4_grouped.hpp).  The operands are the models' operands stacked:
+// w0 [n_models][3][C/16][64][8], w [n_models][2 n_blocks][9][C/16][C/32][64][8], bias [n_models][1 + 2 n_blocks][C].  ONE
+// workgroup shape per channel count -- the wide launches' (16 boards at 32 channels, 8 at 64): every shape computes the same bits.
+int c4_conv_tower_bf16_grouped(const void* planes_dev, const void* w0_dev, const void* w_dev, const float* bias_dev, const uint32_t* seg_start_dev,
+                               uint32_t n_models, uint32_t rows_cap, uint32_t channels, uint32_t n_blocks, void* out_dev, void* stream) {
+  if (!planes_dev || !w0_dev || !bias_dev || !out_dev || !seg_start_dev || (n_blocks && !w_dev)) return c4host::fail(C4_ERR_BAD_ARG, "c4_conv_tower_bf16_grouped: null argument");
+  if (channels != 32 && channels != 64) return c4host::fail(C4_ERR_BAD_ARG, "c4_conv_tower_bf16_grouped: channels must be 32 or 64");
+  if (n_models == 0 || n_models > C4_ROUTE_MAX_MODELS) return c4host::fail(C4_ERR_BAD_ARG, "c4_conv_tower_bf16_grouped: n_models must be between 1 and C4_ROUTE_MAX_MODELS");
+  if (rows_cap % C4_GROUPED_ROW_ALIGN) return c4host::fail(C4_ERR_BAD_ARG, "c4_conv_tower_bf16_grouped: rows_cap must be a multiple of C4_GROUPED_ROW_ALIGN");
+  if (rows_cap == 0) return C4_OK;
+  const int device = c4host::stream_device((hipStream_t)stream);
+  c4host::DeviceGuard guard(device);
+  if (guard.error() != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_conv_tower_bf16_grouped: hipSetDevice: ") + hipGetErrorString(guard.error()));
+  TowerParams p{(const uint16_t*)planes_dev, (const bf16x8*)w0_dev, (const bf16x8*)w_dev, bias_dev, (uint16_t*)out_dev, rows_cap, n_blocks};
+  static_assert(C4_GROUPED_ROW_ALIGN % 16 == 0, "no tower workgroup straddles two segments");
+  if (channels == 32) return launch_tower<32, 16, 512, 1>(p, rows_cap, (hipStream_t)stream, device, seg_start_dev, n_models);
+  return launch_tower<64, 8, 512, 2, true>(p, rows_cap, (hipStream_t)stream, device, seg_start_dev, n_models);
 }
 
 }  // extern "C"
@@ -945,6 +980,21 @@ __global__ __launch_bounds__(64 * kHeadWaves, 1) void c4_head_out_mfma_kernel(
   c4ho::head_out_block<kRows>(sh, hp, hv, wp, wv, bp, bv, n_boards, f8, sp8, sv8, logprobs, q, blockIdx.x);
 }
 
+
+// The grouped form (c4_head_out_bf16_grouped): the workgroup's 16 rows belong to ONE model (segments are multiples of
+// C4_GROUPED_ROW_ALIGN rows); its output layers are the model's slices of the stacked operands, and the nine outputs of a row go
+// to answers[row][9].  The same device code, so the same bits as c4_head_out_mfma_kernel with that model's operands.
+__global__ __launch_bounds__(64 * kHeadWaves, 1) void c4_head_out_grouped_kernel(
+    const uint4* __restrict__ hp, const uint4* __restrict__ hv, const uint4* __restrict__ wp, const uint4* __restrict__ wv,
+    const float* __restrict__ bp, const float* __restrict__ bv, uint32_t rows_cap, uint32_t f8, uint32_t sp8, uint32_t sv8,
+    float* __restrict__ answers, const uint32_t* __restrict__ seg_start, uint32_t n_models) {
+  __shared__ c4ho::Shared sh;
+  const int model = c4grp::Segments{seg_start, n_models}.model_of(blockIdx.x * 16);
+  if (model < 0) return;
+  c4ho::head_out_block<16, true>(sh, hp, hv, wp + (size_t)model * 7 * f8, wv + (size_t)model * 2 * f8, bp + model * 7, bv + model * 2, rows_cap, f8, sp8, sv8,
+                                 answers, nullptr, blockIdx.x);
+}
+
 }  // namespace
 
 namespace {
@@ -1018,5 +1068,29 @@ extern "C" int c4_head_out_bf16(const void* hidden_policy_dev, const void* hidde
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_head_out_bf16 launch: ") + hipGetErrorString(e));
+  return C4_OK;
+}
+
+// c4_head_out_bf16 for a batch whose rows are grouped by model: w_* bf16 [n_models][7|2][features], b_* f32 [n_models][7|2];
+// writes answers f32 [rows_cap][9] (7 log-probabilities, q_penalty, q_no_penalty).  features % 1 344 == 0 (the MFMA form).
+extern "C" int c4_head_out_bf16_grouped(const void* hidden_policy_dev, const void* hidden_value_dev, const void* w_policy_dev, const void* w_value_dev,
+                                        const float* b_policy_dev, const float* b_value_dev, const uint32_t* seg_start_dev, uint32_t n_models,
+                                        uint32_t rows_cap, uint32_t features, uint32_t policy_row_stride, uint32_t value_row_stride, float* answers_dev,
+                                        void* stream) {
+  if (!hidden_policy_dev || !hidden_value_dev || !w_policy_dev || !w_value_dev || !b_policy_dev || !b_value_dev || !answers_dev || !seg_start_dev)
+    return c4host::fail(C4_ERR_BAD_ARG, "c4_head_out_bf16_grouped: null argument");
+  if (features % 8 != 0 || policy_row_stride % 8 != 0 || value_row_stride % 8 != 0 || (features / 8) % (4 * kHeadSteps * kHeadWaves) != 0)
+    return c4host::fail(C4_ERR_BAD_ARG, "c4_head_out_bf16_grouped: features must be a multiple of 1 344 (42 x 32 channels) and the row strides of 8 elements");
+  if (n_models == 0 || n_models > C4_ROUTE_MAX_MODELS) return c4host::fail(C4_ERR_BAD_ARG, "c4_head_out_bf16_grouped: n_models must be between 1 and C4_ROUTE_MAX_MODELS");
+  if (rows_cap % C4_GROUPED_ROW_ALIGN) return c4host::fail(C4_ERR_BAD_ARG, "c4_head_out_bf16_grouped: rows_cap must be a multiple of C4_GROUPED_ROW_ALIGN");
+  if (rows_cap == 0) return C4_OK;
+  const int device = c4host::stream_device((hipStream_t)stream);
+  c4host::DeviceGuard guard(device);
+  if (guard.error() != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_head_out_bf16_grouped: hipSetDevice: ") + hipGetErrorString(guard.error()));
+  c4_head_out_grouped_kernel<<<dim3(rows_cap / 16), dim3(64 * kHeadWaves), 0, (hipStream_t)stream>>>(
+      (const uint4*)hidden_policy_dev, (const uint4*)hidden_value_dev, (const uint4*)w_policy_dev, (const uint4*)w_value_dev, b_policy_dev, b_value_dev,
+      rows_cap, features / 8, policy_row_stride / 8, value_row_stride / 8, answers_dev, seg_start_dev, n_models);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_head_out_bf16_grouped launch: ") + hipGetErrorString(e));
   return C4_OK;
 }

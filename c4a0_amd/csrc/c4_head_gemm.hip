@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "../../include/c4a0_hip.h"
+#include "c4_grouped.hpp"
 #include "c4_host.hpp"
 #include "c4_timeline.hpp"
 
@@ -206,8 +207,12 @@ __device__ __forceinline__ void store_wave_tile(const f32x4 (&acc)[TN][TM], cons
 // three full stages (168 KB) do not fit a CU's 160 KB: 3 x 32 + 2 x 24 = 144 KB.  Per k-tile a wavefront issues the W pieces of
 // k-tile kt + 1 FIRST (they have the rest of this k-tile to land), then the X pieces of k-tile kt + 2.  Same LDS image per
 // stage, same fragment reads, same MFMA order: same bits.
-template <int BM, int BN, int WM, int WN, int NSTAGE, int MINW, int NLOAD = 0, int STAG = 0, int WST = 0>
-__global__ __launch_bounds__(64 * (WM * WN + NLOAD), MINW) void c4_head_gemm_kernel(C4_GEMM_ARGS) {
+// GA: nothing (c4_linear_bf16's kernels: the arguments and the code they have always had), or the grouped form's two further
+// arguments (const uint32_t* seg_start, uint32_t n_models) -- c4_linear_bf16_grouped: the workgroup finds the model whose row
+// segment holds its first row, moves w and bias to that model's layer (the layers are stacked, [n_models][N][K] and [n_models][N])
+// and runs the same code; past the last segment it writes nothing.
+template <int BM, int BN, int WM, int WN, int NSTAGE, int MINW, int NLOAD = 0, int STAG = 0, int WST = 0, typename... GA>
+__global__ __launch_bounds__(64 * (WM * WN + NLOAD), MINW) void c4_head_gemm_kernel(C4_GEMM_ARGS, GA... a_group) {
   C4_GEMM_UNPACK();
   constexpr int kWaves = WM * WN;                             // computing wavefronts
   constexpr int kIssuers = NLOAD ? NLOAD : kWaves;            // wavefronts that issue DMA pieces
@@ -241,6 +246,12 @@ __global__ __launch_bounds__(64 * (WM * WN + NLOAD), MINW) void c4_head_gemm_ker
   int tm, tn;
   tile_of_block(blockIdx.x, p.xcd_mask, p.xcd_shift, p.xn_log2, p.rm, p.rn, p.rn_magic, tm, tn);
   const int tm0 = tm * BM, tn0 = tn * BN;
+  if constexpr (sizeof...(GA) != 0) {
+    const int model = c4grp::Segments{a_group...}.model_of((uint32_t)tm0);
+    if (model < 0) return;                                    // (the whole workgroup: no barrier has been met)
+    p.w += (size_t)model * p.N * p.K;
+    p.bias += (size_t)model * p.N;
+  }
 
   // ---- DMA source offsets (bytes from x / w) of this lane for its L pieces of a k-tile; a k-tile
   // later they are 128 bytes further.  Piece c < BM/8 is rows 8c..8c+7 of the X tile, else of the W tile.
@@ -726,8 +737,8 @@ inline uint32_t set_tile_order(GemmParams& p, uint32_t tiles_m, uint32_t tiles_n
   return tiles_m * tiles_n;
 }
 
-template <int BM, int BN, typename K>
-int launch_common(K k, GemmParams p, int threads, int lds_bytes, hipStream_t stream, int device) {
+template <int BM, int BN, typename K, typename... GA>
+int launch_common(K k, GemmParams p, int threads, int lds_bytes, hipStream_t stream, int device, GA... group) {
   if (lds_bytes > 64 * 1024) {
     const hipError_t e = c4host::opt_in_lds((const void*)k, lds_bytes, device);
     if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_linear_bf16: LDS opt-in: ") + hipGetErrorString(e));
@@ -736,7 +747,7 @@ int launch_common(K k, GemmParams p, int threads, int lds_bytes, hipStream_t str
   if (p.rm > 0xFFFFu || p.rn > 0xFFFFu)   // rm and rn travel as 16-bit halves of one kernel argument
     return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16: more than 65 535 tiles along one dimension of an XCD's rectangle (m too large for this tile)");
   k<<<dim3(tiles), dim3(threads), lds_bytes, stream>>>(p.x, p.w, p.bias, p.y, p.M, p.N | (p.K << 16), p.ldx | (p.ldy << 16),
-                                                         (p.relu ? 1u : 0u) | (p.xn_log2 << 8) | (p.xcd_mask << 16) | (p.xcd_shift << 24), p.rm | (p.rn << 16), p.rn_magic);
+                                                         (p.relu ? 1u : 0u) | (p.xn_log2 << 8) | (p.xcd_mask << 16) | (p.xcd_shift << 24), p.rm | (p.rn << 16), p.rn_magic, group...);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_linear_bf16 launch: ") + hipGetErrorString(e));
   return C4_OK;
@@ -913,4 +924,29 @@ extern "C" int c4_linear_bf16(const void* x_dev, const void* w_dev, const float*
     case 53: return launch_common<256, 192>(c4_head_gemm4_kernel<256, 192>, p, 256, 2 * (256 + 192) * BK * 2, st, device);   // round 5: 4 wavefronts (128 x 96 each), operands staged through registers, 2-deep ring, 112 KB
     default: return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16: unknown config");
   }
+}
+
+// c4_linear_bf16 for a batch whose rows are grouped by model (c4_grouped.hpp): w bf16 [n_models][n][k], bias f32 [n_models][n], the
+// launch covers rows_cap rows.  ONE tile configuration -- c4_linear_bf16's config 11, 128 x 192 on 8 wavefronts, whose 128 rows
+// C4_GROUPED_ROW_ALIGN is a multiple of; every configuration computes the same bits.  The other limits are c4_linear_bf16's.
+extern "C" int c4_linear_bf16_grouped(const void* x_dev, const void* w_dev, const float* bias_dev, void* y_dev, const uint32_t* seg_start_dev, uint32_t n_models,
+                                      uint32_t rows_cap, uint32_t n, uint32_t k, uint32_t ldx, uint32_t ldy, uint32_t relu, void* stream) {
+  if (!x_dev || !w_dev || !bias_dev || !y_dev || !seg_start_dev) return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: null argument");
+  if (k == 0 || k % BK) return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: K must be a positive multiple of 64");
+  if (n == 0 || n % 192) return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: N must be a positive multiple of 192 (42 x C features, C a multiple of 32)");
+  if (ldx < k || ldy < n || ldx % 8 || ldy % 8 || ((uintptr_t)y_dev & 15) || ((uintptr_t)x_dev & 15))
+    return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: row strides must cover a row and keep rows 16-byte aligned (x and y)");
+  if ((uint64_t)rows_cap * ldx * 2 >= (1ull << 31) || (uint64_t)n * k * 2 >= (1ull << 31))
+    return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: operands are addressed with 31-bit byte offsets (< 2 GiB; the weights: each model's layer)");
+  if (n >= 65536 || k >= 65536 || ldx >= 65536 || ldy >= 65536) return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: n, k and the row strides must be below 65 536 (packed kernel arguments)");
+  if (n_models == 0 || n_models > C4_ROUTE_MAX_MODELS) return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: n_models must be between 1 and C4_ROUTE_MAX_MODELS");
+  if (rows_cap % C4_GROUPED_ROW_ALIGN) return c4host::fail(C4_ERR_BAD_ARG, "c4_linear_bf16_grouped: rows_cap must be a multiple of C4_GROUPED_ROW_ALIGN");
+  if (rows_cap == 0) return C4_OK;
+  const int device = c4host::stream_device((hipStream_t)stream);
+  c4host::DeviceGuard guard(device);
+  if (guard.error() != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string("c4_linear_bf16_grouped: hipSetDevice: ") + hipGetErrorString(guard.error()));
+  GemmParams p{(const uint16_t*)x_dev, (const uint16_t*)w_dev, bias_dev, (uint16_t*)y_dev, rows_cap, n, k, ldx, ldy, relu, 0, 0, 0, 0, 0, 0};
+  static_assert(C4_GROUPED_ROW_ALIGN % 128 == 0, "no GEMM workgroup straddles two segments");
+  return launch_common<128, 192>(c4_head_gemm_kernel<128, 192, 2, 4, 3, 1, 0, 0, 0, const uint32_t*, uint32_t>, p, 64 * 8, 3 * (128 + 192) * BK * 2, (hipStream_t)stream,
+                                 device, seg_start_dev, n_models);
 }

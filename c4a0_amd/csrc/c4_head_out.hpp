@@ -27,7 +27,9 @@ struct Shared {
 // kRows = boards per workgroup: 16 (every row of the MFMA tile a board) or 8 (rows 8..15 repeat rows 0..7).
 // Called by all 64 * kHeadWaves threads of workgroup `block`.  On return the boards' outputs are in global memory and in
 // sh.res (visible to the workgroup after the caller's next barrier).
-template <int kRows>
+// kRow9: the nine outputs of board g go to logprobs[9 g .. 9 g + 8] (the row format of c4_session_step_gather and
+// c4_session_scatter_outputs; q is unused) instead of logprobs[7 g ..] and q[2 g ..]: c4_head_out_bf16_grouped.
+template <int kRows, bool kRow9 = false>
 __device__ __forceinline__ void head_out_block(Shared& sh, const uint4* __restrict__ hp, const uint4* __restrict__ hv, const uint4* __restrict__ wp,
                                                const uint4* __restrict__ wv, const float* __restrict__ bp, const float* __restrict__ bv, uint32_t n_boards,
                                                uint32_t f8, uint32_t sp8, uint32_t sv8, float* __restrict__ logprobs, float* __restrict__ q, uint32_t block) {
@@ -100,6 +102,15 @@ __device__ __forceinline__ void head_out_block(Shared& sh, const uint4* __restri
     for (int o = 0; o < 7; o++) sh.res[b][o] = v[o] - lse;
     sh.res[b][7] = q0;
     sh.res[b][8] = q1;
+    if constexpr (kRow9) {
+      if (gb < n_boards) {
+#pragma unroll
+        for (int o = 0; o < 7; o++) logprobs[(size_t)gb * 9 + o] = v[o] - lse;
+        logprobs[(size_t)gb * 9 + 7] = q0;
+        logprobs[(size_t)gb * 9 + 8] = q1;
+      }
+      return;
+    }
     if (gb < n_boards) {
 #pragma unroll
       for (int o = 0; o < 7; o++) logprobs[(size_t)gb * 7 + o] = v[o] - lse;

@@ -617,6 +617,114 @@ class InferenceNet:
     __call__ = forward
 
 
+class GroupedNets:
+    """Several bf16 `InferenceNet`s of ONE architecture as the operands of the grouped chain (c4_conv_tower_bf16_grouped,
+    c4_linear_bf16_grouped, c4_head_out_bf16_grouped; include/c4a0_hip.h): every weight / bias operand of the chain stacked along a
+    new leading dimension in the order of `ids` -- tw0, tw, tbias, the merged first layer (w1, b1), the heads' further hidden layers
+    (pol_w / pol_b, val_w / val_b: one stacked tensor per layer) and the output layers with their f32 biases.  `forward` runs the
+    chain on a batch whose rows are grouped by model (DeviceSession.route_leaves): a real row's nine outputs are bit-identical to
+    what its model's InferenceNet computes for it.  What tournaments replay from a HIP graph (api._GroupedModelEvaluator)."""
+
+    @staticmethod
+    def refusal(nets: dict) -> Optional[str]:
+        """None, or the reason these evaluators cannot be grouped (then a tournament takes the eager path).  Needs no GPU."""
+        from ._lib import ROUTE_MAX_MODELS
+
+        evs = list(nets.values())
+        if not evs:
+            return "no evaluators"
+        for ev in evs:
+            if not isinstance(ev, InferenceNet):
+                return "an evaluator is not a c4a0_amd.nn.InferenceNet"
+            if type(ev).forward is not InferenceNet.forward or type(ev).__call__ is not InferenceNet.__call__:
+                return "an evaluator overrides InferenceNet.forward (it must see every evaluation)"
+        if len(evs) > ROUTE_MAX_MODELS:
+            return f"more than {ROUTE_MAX_MODELS} models"
+        a = evs[0]
+        for ev in evs:
+            if len(ev.pol_w) < 2 or len(ev.val_w) < 2 or ev.merged_w1 is None:
+                return "a head without a hidden layer (the grouped chain starts with the merged first layer of both heads)"
+        for ev in evs[1:]:
+            if ev.channels != a.channels:
+                return f"the architectures differ: {a.channels} and {ev.channels} channels"
+            if ev.n_blocks != a.n_blocks:
+                return f"the architectures differ: {a.n_blocks} and {ev.n_blocks} residual blocks"
+            if (len(ev.pol_w), len(ev.val_w)) != (len(a.pol_w), len(a.val_w)):
+                return f"the architectures differ: head depths (policy, value) {(len(a.pol_w), len(a.val_w))} and {(len(ev.pol_w), len(ev.val_w))}"
+        for ev in evs[1:]:
+            if ev.device != a.device:
+                return f"the evaluators are on different devices ({a.device}, {ev.device})"
+        for ev in evs:
+            if not ev.fused_step_ok or ev.path != "hip" or ev.dtype != torch.bfloat16 or not ev.batch_invariant:
+                return "an evaluator does not run the hand-written bf16 kernels (path 'hip', bfloat16, batch-invariant)"
+            if ev.gemm_config != (0, 0) or ev.tower_config or not ev.use_loader_waves or not ev.wide_tiles_r5 or ev.stage_hook is not None:
+                return "an evaluator carries a measurement switch (tile configuration, stage hook)"
+        return None
+
+    def __init__(self, nets: dict):
+        why = GroupedNets.refusal(nets)
+        if why is not None:
+            raise ValueError(f"GroupedNets: {why}")
+        self.ids = [int(k) & ((1 << 64) - 1) for k in nets]
+        evs = list(nets.values())
+        a = evs[0]
+        self.L: ctypes.CDLL = lib()
+        self.device, self.dtype, self.channels, self.n_blocks, self.n_models = a.device, torch.bfloat16, a.channels, a.n_blocks, len(evs)
+        self.row_align = int(self.L.c4_grouped_row_align())
+        stack = lambda ts: torch.stack([t for t in ts]).contiguous()
+        b32 = lambda ev, b: ev.chain._bias32[b.data_ptr()]     # the f32 copy c4_linear_bf16's epilogue is handed
+        self.tw0, self.tw, self.tbias = stack(ev.tw0 for ev in evs), stack(ev.tw for ev in evs), stack(ev.tbias for ev in evs)
+        self.w1, self.b1 = stack(ev.merged_w1 for ev in evs), stack(b32(ev, ev.merged_b1) for ev in evs)
+        self.pol_w = [stack(ev.pol_w[i] for ev in evs) for i in range(1, len(a.pol_w) - 1)]
+        self.pol_b = [stack(b32(ev, ev.pol_b[i]) for ev in evs) for i in range(1, len(a.pol_w) - 1)]
+        self.val_w = [stack(ev.val_w[i] for ev in evs) for i in range(1, len(a.val_w) - 1)]
+        self.val_b = [stack(b32(ev, ev.val_b[i]) for ev in evs) for i in range(1, len(a.val_w) - 1)]
+        self.pol_out_w, self.val_out_w = stack(ev.pol_w[-1] for ev in evs), stack(ev.val_w[-1] for ev in evs)
+        self.pol_out_b, self.val_out_b = stack(ev.pol_b32 for ev in evs), stack(ev.val_b32 for ev in evs)
+        self.model_ids = torch.tensor(np.array(self.ids, dtype=np.uint64).view(np.int64), dtype=torch.int64, device=self.device)
+
+    def buffers(self, rows_cap: int) -> dict:
+        """The chain's activations for batches of rows_cap rows: allocated once, so that a captured round owns no allocation."""
+        f = 42 * self.channels
+        mk = lambda *shape, dtype=torch.bfloat16: torch.zeros(shape, dtype=dtype, device=self.device)
+        return {"rows_cap": int(rows_cap), "planes": mk(rows_cap, 2, 6, 7), "feat": mk(rows_cap, f), "h1": mk(rows_cap, 2 * f),
+                "p": [mk(rows_cap, f) for _ in range(min(2, len(self.pol_w)))], "v": [mk(rows_cap, f) for _ in range(min(2, len(self.val_w)))],
+                "answers": mk(rows_cap, 9, dtype=torch.float32)}
+
+    def tower(self, planes, seg_start, out):
+        check(self.L.c4_conv_tower_bf16_grouped(planes.data_ptr(), self.tw0.data_ptr(), self.tw.data_ptr() if self.n_blocks else None, self.tbias.data_ptr(),
+                                                seg_start.data_ptr(), self.n_models, planes.shape[0], self.channels, self.n_blocks, out.data_ptr(),
+                                                _stream(self.device)))
+        return out
+
+    def linear_relu(self, x, w, b, seg_start, out):
+        assert x.stride(1) == 1 and out.stride(1) == 1
+        check(self.L.c4_linear_bf16_grouped(x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), seg_start.data_ptr(), self.n_models, x.shape[0],
+                                            w.shape[1], w.shape[2], x.stride(0), out.stride(0), 1, _stream(self.device)))
+        return out
+
+    def head_out(self, p, v, seg_start, answers):
+        assert p.stride(1) == 1 and v.stride(1) == 1
+        check(self.L.c4_head_out_bf16_grouped(p.data_ptr(), v.data_ptr(), self.pol_out_w.data_ptr(), self.val_out_w.data_ptr(), self.pol_out_b.data_ptr(),
+                                              self.val_out_b.data_ptr(), seg_start.data_ptr(), self.n_models, p.shape[0], p.shape[1], p.stride(0), v.stride(0),
+                                              answers.data_ptr(), _stream(self.device)))
+        return answers
+
+    @torch.no_grad()
+    def forward(self, buf: dict, seg_start: torch.Tensor) -> torch.Tensor:
+        """buf["planes"] (rows grouped by model, segment bounds seg_start int32[n_models + 1] on the device) -> buf["answers"]
+        f32 [rows_cap, 9]: InferenceNet.forward's chain, one grouped launch per layer."""
+        x = self.tower(buf["planes"], seg_start, buf["feat"])
+        h = self.linear_relu(x, self.w1, self.b1, seg_start, buf["h1"])
+        f = h.shape[1] // 2
+        p, v = h[:, :f], h[:, f:]
+        for i, (w, b) in enumerate(zip(self.pol_w, self.pol_b)):
+            p = self.linear_relu(p, w, b, seg_start, buf["p"][i & 1])
+        for i, (w, b) in enumerate(zip(self.val_w, self.val_b)):
+            v = self.linear_relu(v, w, b, seg_start, buf["v"][i & 1])
+        return self.head_out(p, v, seg_start, buf["answers"])
+
+
 class GraphedEvaluator:
     """The evaluator captured once in a HIP graph: one replay per step instead of ~25 eager
     launches.  Reads `planes`, writes `logprobs` and `q` (the session's bound tensors)."""

@@ -55,6 +55,12 @@ def capture(graph: "torch.cuda.CUDAGraph", stream: Optional[torch.cuda.Stream] =
 LEAN_CAPTURE = True   # (False: torch.cuda.graph's own entry, the A/B)
 
 
+def route_rows_cap(n_slots: int, n_models: int, align: int) -> int:
+    """Rows a routed batch must have room for (c4_session_route_leaves): every model's count is rounded up to `align`, which adds
+    at most align - 1 pad rows per model, and the total is a multiple of align."""
+    return -(-(int(n_slots) + int(n_models) * (int(align) - 1)) // int(align)) * int(align)
+
+
 class DeviceSession:
     def __init__(self, n_slots: int, n_mcts_iterations: int, c_exploration: float, c_ply_penalty: float,
                  device: Optional[torch.device] = None, planes_dtype: torch.dtype = torch.float32,
@@ -164,6 +170,19 @@ class DeviceSession:
         self.leaf_models = models
         return self.leaf_models
 
+    def route_leaves(self, model_ids: torch.Tensor, align: int, planes_out: torch.Tensor, inverse: torch.Tensor,
+                     seg_start: torch.Tensor, n_unrouted: torch.Tensor):
+        """c4_session_route_leaves: the resident games' leaves as one batch grouped by the model that must answer them
+        (bind_leaf_models() first; bf16 planes).  All arguments are device tensors: model_ids int64[n_models] (the ids as 64-bit
+        patterns), planes_out bf16 [rows_cap, 2, 6, 7] with rows_cap >= route_rows_cap(n_slots, n_models, align), inverse
+        int32[n_slots] (a slot's row, -1 = 0xFFFFFFFF for idle or unrouted slots), seg_start int32[n_models + 1], n_unrouted int32[1].
+        On the bound stream, asynchronous, capturable; no count reaches the host."""
+        if planes_out.dtype != torch.bfloat16 or not planes_out.is_contiguous() or inverse.numel() < self.n_slots or seg_start.numel() < model_ids.numel() + 1:
+            raise ValueError("route_leaves: planes_out must be contiguous bf16, inverse [n_slots], seg_start [n_models + 1]")
+        check(self.L.c4_session_route_leaves(self._h, C.c_void_p(model_ids.data_ptr()), int(model_ids.numel()), int(align), C.c_void_p(planes_out.data_ptr()),
+                                             int(planes_out.shape[0]), C.c_void_p(inverse.data_ptr()), C.c_void_p(seg_start.data_ptr()),
+                                             C.c_void_p(n_unrouted.data_ptr())))
+
     def arena(self) -> dict:
         """How the tree arena was sized: {"bytes", "blocks_per_slot", "reclaim_half_blocks"} (the last 0 = never reclaimed)."""
         b, bps, half = C.c_uint64(), C.c_uint32(), C.c_uint32()
@@ -202,7 +221,7 @@ class DeviceSession:
                                                   C.c_void_p(wv.data_ptr()), C.c_void_p(bp.data_ptr()), C.c_void_p(bv.data_ptr()),
                                                   p.shape[1], p.stride(0), v.stride(0)))
             return
-        if hasattr(evaluator, "round") and getattr(evaluator, "s", None) is self:   # the numpy-callback evaluator: answers handed over in the step's launch
+        if hasattr(evaluator, "round") and getattr(evaluator, "s", None) is self:   # the numpy-callback evaluator and the grouped tournament evaluator: answers handed over in the step's launch
             evaluator.round()
             return
         self.evaluate(evaluator)

@@ -24,10 +24,10 @@ extern "C" {
 #endif
 
 /* Version of THIS interface: bumped whenever a signature or a struct layout below changes (version 3 added `config` in the
- * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED, version 11 the f32 evaluator c4_conv_tower_f32 / c4_linear_f32 / c4_head_out_f32, version 12 C4_FLAG_SEARCH / c4_search_positions_bf16, version 13 C4_FLAG_HOLD / c4_session_set_iterations / c4_session_hold_resume / c4_session_snapshot / c4_session_hold_poll).  A consumer compiled against this header checks it once at start-up --
+ * middle of c4_conv_tower_bf16's arguments, version 5 c4_session_step_head_out, version 8 the host-side record codecs c4_records_to_cbor / c4_cbor_to_records / c4_shuffle_games, version 9 c4_play_games_bf16, version 10 c4_play_games_cancel / C4_ERR_CANCELLED, version 11 the f32 evaluator c4_conv_tower_f32 / c4_linear_f32 / c4_head_out_f32, version 12 C4_FLAG_SEARCH / c4_search_positions_bf16, version 13 C4_FLAG_HOLD / c4_session_set_iterations / c4_session_hold_resume / c4_session_snapshot / c4_session_hold_poll, version 14 c4_session_route_leaves and the grouped bf16 chain c4_conv_tower_bf16_grouped / c4_linear_bf16_grouped / c4_head_out_bf16_grouped / c4_grouped_row_align).  A consumer compiled against this header checks it once at start-up --
  * `if (c4_abi_version() != C4_ABI_VERSION) refuse` -- because the dynamic linker compares names, not signatures
  * (tests/abi_consumer*.c and c4a0_amd/_lib.py do).  No reference counterpart: the reference's boundary is PyO3. */
-#define C4_ABI_VERSION 13
+#define C4_ABI_VERSION 14
 
 #define C4_N_COLS 7          /* rust/src/c4r.rs:45, lib.rs:28 */
 #define C4_N_ROWS 6          /* rust/src/c4r.rs:44, lib.rs:29 */
@@ -489,6 +489,29 @@ int c4_session_scatter_outputs(c4_session* s, const uint32_t* inverse_dev, const
  * updated: callers that watch them keep the two entry points.  Every configuration of the session (noise, cache, timing). */
 int c4_session_step_gather(c4_session* s, const uint32_t* inverse_dev, const float* answers, uint32_t n_unique);
 
+/* ---- tournaments from a HIP graph (ABI 14): route the leaves of a multi-model session by model, on the device ---- */
+#define C4_ROUTE_MAX_MODELS 32    /* models one routed batch may hold */
+#define C4_GROUPED_ROW_ALIGN 128  /* c4_grouped_row_align(): the rows per workgroup of every grouped kernel divide it */
+/* The resident games' leaves as ONE batch of rows_cap rows grouped by the model that must answer them (c4_session_bind_leaf_models:
+ * mcts.rs:70-76), for the grouped bf16 chain below.  On the session's stream, no synchronisation, may be captured in a HIP graph;
+ * no count reaches the host.  A session of games with bound leaf models and bf16 planes (planes_dtype 1); search and hold sessions
+ * are refused.  For slot g:
+ *   group     the index m with model_ids_dev[m] == the slot's leaf model.  An idle slot (decided from the slot, as
+ *             c4_session_leaf_keys does: id 0 may be a real player) is not routed: inverse_dev[g] = 0xFFFFFFFF.  A slot whose id is
+ *             not in the table is not routed either and is counted in *n_unrouted_dev.
+ *   segments  seg_start_dev[0] = 0, seg_start_dev[m + 1] = seg_start_dev[m] + round_up(count_m, align); a model without rows has an
+ *             empty segment.
+ *   rows      inverse_dev[g] = seg_start_dev[m] + the slot's rank among the routed slots of model m in ASCENDING SLOT ORDER: the
+ *             batch is a function of the games alone.
+ *   planes    planes_out_dev[inverse_dev[g]] = the slot's 84 bf16 plane values; the pad rows between a segment's last row and the
+ *             next segment become empty boards (zeros).  Rows from seg_start_dev[n_models] on are left as they are.
+ * model_ids_dev [n_models], planes_out_dev bf16 [rows_cap][2][6][7], inverse_dev [n_slots], seg_start_dev [n_models + 1] and
+ * n_unrouted_dev [1] are device memory of the session's device.  Refused (C4_ERR_BAD_ARG, the message names the bound): align not
+ * a power of two in 16..256; n_models 0 or above C4_ROUTE_MAX_MODELS; rows_cap < round_up(n_slots + n_models * (align - 1), align)
+ * (the sum of the rounded counts can never exceed it).  For the grouped chain align must be a multiple of c4_grouped_row_align(). */
+int c4_session_route_leaves(c4_session* s, const uint64_t* model_ids_dev, uint32_t n_models, uint32_t align, void* planes_out_dev,
+                            uint32_t rows_cap, uint32_t* inverse_dev, uint32_t* seg_start_dev, uint32_t* n_unrouted_dev);
+
 /* ---- hold sessions (C4_FLAG_HOLD, ABI 13): InteractivePlay's operations for every slot at once ---- */
 /* InteractivePlay::increase_mcts_iters (interactive_play.rs:63-67) as an absolute target: 1 <= n <= the n_mcts_iterations the session
  * was created with (which sizes the arena and the table of logarithms), else C4_ERR_BAD_ARG.  Takes effect with the next launch on
@@ -620,6 +643,31 @@ int c4_head_out_bf16(const void* hidden_policy_dev, const void* hidden_value_dev
                      const void* w_value_dev, const float* b_policy_dev, const float* b_value_dev,
                      uint32_t n_boards, uint32_t features, uint32_t policy_row_stride, uint32_t value_row_stride,
                      float* logprobs_dev, float* q_dev, void* stream);
+
+/* ---- grouped bf16 chain (ABI 14): the three kernels above for a batch whose rows are cut into one segment per model --
+ * seg_start_dev [n_models + 1] in DEVICE memory (c4_session_route_leaves writes it; ascending from 0, every entry a multiple of
+ * c4_grouped_row_align()), model m owns rows seg_start[m] .. seg_start[m + 1] - 1 -- each segment computed with ITS model's
+ * weights, in one launch of a fixed shape that covers rows_cap rows (a multiple of c4_grouped_row_align(), 1 <= n_models <=
+ * C4_ROUTE_MAX_MODELS).  Every weight / bias operand is the models' operands of the ungrouped entry point stacked along a new
+ * leading dimension, one model's operand after the other (the stride per model is the operand's size).  A workgroup finds the m
+ * with seg_start[m] <= its first row < seg_start[m + 1], moves its weight pointers by m strides and runs the ungrouped kernel's
+ * code: a row's outputs are bit-identical to those of the ungrouped entry point run with that model's weights.  Rows at or
+ * beyond seg_start[n_models] are not written; rows of a segment are all computed (pad rows too).  One workgroup shape per kernel
+ * and channel count (all shapes compute the same bits).  No synchronisation; may be captured. */
+int c4_grouped_row_align(void); /* == C4_GROUPED_ROW_ALIGN: a multiple of the tower's boards, the GEMM's rows and the output kernel's rows per workgroup */
+/* c4_conv_tower_bf16: w0_dev [n_models][3][C/16][64][8], w_dev [n_models][2 n_blocks][9][C/16][C/32][64][8], bias_dev
+ * [n_models][1 + 2 n_blocks][C]; out_dev bf16 [rows_cap][42][channels]. */
+int c4_conv_tower_bf16_grouped(const void* planes_dev, const void* w0_dev, const void* w_dev, const float* bias_dev, const uint32_t* seg_start_dev,
+                               uint32_t n_models, uint32_t rows_cap, uint32_t channels, uint32_t n_blocks, void* out_dev, void* stream);
+/* c4_linear_bf16: w_dev bf16 [n_models][n][k], bias_dev f32 [n_models][n]; x_dev may be a column range of a wider tensor (ldx > k). */
+int c4_linear_bf16_grouped(const void* x_dev, const void* w_dev, const float* bias_dev, void* y_dev, const uint32_t* seg_start_dev, uint32_t n_models,
+                           uint32_t rows_cap, uint32_t n, uint32_t k, uint32_t ldx, uint32_t ldy, uint32_t relu, void* stream);
+/* c4_head_out_bf16: w_policy_dev bf16 [n_models][7][features], w_value_dev [n_models][2][features], b_policy_dev f32 [n_models][7],
+ * b_value_dev [n_models][2]; writes answers_dev f32 [rows_cap][9] -- 7 log-probabilities, q_penalty, q_no_penalty: the row format
+ * of c4_session_step_gather and c4_session_scatter_outputs.  features % 1 344 == 0. */
+int c4_head_out_bf16_grouped(const void* hidden_policy_dev, const void* hidden_value_dev, const void* w_policy_dev, const void* w_value_dev,
+                             const float* b_policy_dev, const float* b_value_dev, const uint32_t* seg_start_dev, uint32_t n_models, uint32_t rows_cap,
+                             uint32_t features, uint32_t policy_row_stride, uint32_t value_row_stride, float* answers_dev, void* stream);
 
 /* ---- f32 evaluator (ABI 11): ConnectFourNet in f32 (the reference trains and evaluates in f32, nn.py:119-130) on gfx950's exact-f32
  * MFMA (v_mfma_f32_16x16x4_f32), for any width C = 1..64 (padded to Cp = 16 ceil(C / 16)), any number of residual blocks and any head
