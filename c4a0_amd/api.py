@@ -340,6 +340,8 @@ def _native_loop_refusal(evaluator, device, planes_dtype, concurrent_sessions) -
 
     if not isinstance(evaluator, InferenceNet):
         return "the evaluator is not a c4a0_amd.nn.InferenceNet"
+    if getattr(evaluator, "head_dtype", None) is not None:
+        return "fp8 hidden layers run through the Python host loop"
     if not evaluator.fused_step_ok:           # (a subclass that overrides forward / __call__ must see every evaluation)
         return "the evaluator overrides InferenceNet.forward, or does not run on the hand-written kernels"
     if evaluator.path != "hip" or evaluator.dtype != torch.bfloat16 or evaluator.merged_w1 is None:

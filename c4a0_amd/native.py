@@ -22,6 +22,8 @@ def network_struct(net) -> _lib.NetworkBf16:
     """c4_network_bf16 over the tensors of a c4a0_amd.nn.InferenceNet (which must stay alive while the struct is used)."""
     import torch
 
+    if getattr(net, "head_dtype", None) is not None:
+        raise TypeError("the native host loop takes a bf16 network: fp8 hidden layers run through the Python host loop")
     if not (getattr(net, "path", None) == "hip" and net.dtype == torch.bfloat16 and net.merged_w1 is not None):
         raise TypeError("the native host loop takes a bf16 c4a0_amd.nn.InferenceNet on the hand-written kernels whose heads both have a hidden layer")
     s = _lib.NetworkBf16()

@@ -289,6 +289,193 @@ class _Bf16Chain(_TorchChain):
         return lp, q
 
 
+# ---------------------------------------------------------------------------------------------- fp8 hidden layers (opt-in)
+# include/c4a0_hip.h, "fp8 hidden layers": the numerics contract.  The helpers below need no GPU.
+FP8_MAX = 448.0
+
+
+def to_fp8_e4m3(t_f32: torch.Tensor) -> torch.Tensor:
+    """The contract's q8: f32 -> OCP e4m3fn codes (uint8).  NaN -> 0x7F; otherwise clamp to [-448, 448], then round to nearest, ties
+    to even; subnormals and the sign of zero are kept."""
+    t = t_f32.to(torch.float32)
+    nan = torch.isnan(t)
+    c = torch.clamp(torch.where(nan, torch.zeros_like(t), t), -FP8_MAX, FP8_MAX)
+    q = c.to(torch.float8_e4m3fn).view(torch.uint8)
+    return torch.where(nan, torch.full_like(q, 0x7F), q)
+
+
+def _pow2_exponent_below(a: torch.Tensor, limit_m: float, limit_e: int) -> torch.Tensor:
+    """Per element of the positive finite float64 a: the largest integer e with a 2^e <= limit_m 2^limit_e (0.5 <= limit_m < 1)."""
+    m, ex = torch.frexp(a)                                        # a = m 2^ex, 0.5 <= m < 1
+    return torch.where(m <= limit_m, limit_e - ex, limit_e - 1 - ex).to(torch.int64)
+
+
+def quantize_head_weights(w_f32: torch.Tensor):
+    """(Wq uint8 [N, K], e_w int32 [N]) of the BN-folded f32 weights W [N, K]: per output row n, e_w[n] is the largest integer in
+    [-64, 64] with max_k |W[n][k]| 2^e_w[n] <= 448 (an all-zero row: 0) and Wq[n][k] = q8(W[n][k] 2^e_w[n]).  Powers of two: the
+    scaling is exact, only range is adapted."""
+    w = w_f32.detach().to("cpu", torch.float64)
+    amax = w.abs().amax(dim=1)
+    ok = (amax > 0) & torch.isfinite(amax)
+    e = _pow2_exponent_below(torch.where(ok, amax, torch.ones_like(amax)), 0.875, 9)       # 448 = 0.875 x 2^9
+    e = torch.where(ok, torch.clamp(e, -64, 64), torch.zeros_like(e))
+    wq = to_fp8_e4m3(torch.ldexp(w, e[:, None]).float())
+    return wq.contiguous(), e.to(torch.int32)
+
+
+def activation_exponent(a: float) -> int:
+    """The e_x of a GEMM input tensor whose calibration rows reach max |x| = a: the largest integer (kept in [-64, 64]) with
+    2 a 2^e_x <= 448, a factor 2 of headroom; 0 for a = 0 (or a non-finite a)."""
+    a = float(a)
+    if not (a > 0.0) or a == float("inf"):
+        return 0
+    e = int(_pow2_exponent_below(torch.tensor([2.0 * a], dtype=torch.float64), 0.875, 9)[0])
+    return max(-64, min(64, e))
+
+
+def _c4_won(stones) -> bool:
+    """Four in a row among the cells `stones` ([6][7] booleans)."""
+    for r in range(N_ROWS):
+        for c in range(N_COLS):
+            if not stones[r][c]:
+                continue
+            for dr, dc in ((0, 1), (1, 0), (1, 1), (1, -1)):
+                if all(0 <= r + i * dr < N_ROWS and 0 <= c + i * dc < N_COLS and stones[r + i * dr][c + i * dc] for i in range(1, 4)):
+                    return True
+    return False
+
+
+def calibration_positions(n: int = 4096, seed: int = 0) -> np.ndarray:
+    """uint64[n, 2] (mask, value) positions for choosing the fp8 activation scales: every position of seeded random legal playouts
+    from the empty board to the end of the game (the empty board included), so all plies are covered.  Pure numpy, deterministic:
+    the scales are a function of (weights, calibration rows) only.  Bit 7 r + c is cell (row r from the bottom, column c); `value`
+    holds the stones of the player to move (c4r.rs:13-17)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = np.zeros((n, 2), dtype=np.uint64)
+    k = 0
+    while k < n:
+        mine = [[False] * N_COLS for _ in range(N_ROWS)]          # the stones of the player to move
+        theirs = [[False] * N_COLS for _ in range(N_ROWS)]
+        heights = [0] * N_COLS
+        while k < n:
+            mask = sum(1 << (7 * r + c) for r in range(N_ROWS) for c in range(N_COLS) if mine[r][c] or theirs[r][c])
+            value = sum(1 << (7 * r + c) for r in range(N_ROWS) for c in range(N_COLS) if mine[r][c])
+            out[k] = (mask, value)
+            k += 1
+            legal = [c for c in range(N_COLS) if heights[c] < N_ROWS]
+            if not legal or _c4_won(theirs):                      # (only the player who just moved can have won)
+                break
+            c = legal[int(rng.integers(len(legal)))]
+            mine[heights[c]][c] = True
+            heights[c] += 1
+            mine, theirs = theirs, mine
+    return out
+
+
+def positions_to_planes(pos: np.ndarray) -> np.ndarray:
+    """uint64[P, 2] (mask, value) -> float32 [P, 2, 6, 7] planes (c4r.rs:378-392: the mover's stones, the opponent's)."""
+    pos = np.asarray(pos, dtype=np.uint64).reshape(-1, 2)
+    bit = np.arange(42, dtype=np.uint64)[None, :]
+    mine = ((pos[:, 1:2] >> bit) & np.uint64(1)).astype(np.float32)
+    opp = (((pos[:, 0:1] ^ pos[:, 1:2]) >> bit) & np.uint64(1)).astype(np.float32)
+    return np.stack([mine, opp], axis=1).reshape(len(pos), 2, N_ROWS, N_COLS)
+
+
+class _Fp8HeadChain(_Bf16Chain):
+    """_Bf16Chain with the heads' hidden layers in OCP e4m3 (c4_quantize_bf16_fp8, c4_linear_fp8; the contract is
+    include/c4a0_hip.h's "fp8 hidden layers").  The tower, the output layers (the bf16 pol_w[-1] / val_w[-1]) and everything the
+    session does with them are the base's.  Per hidden layer it keeps Wq, dq, the f32 bias as folded and the exponents, found by the
+    bf16 weight tensor InferenceNet hands to linear_relu(); the first layer of both heads is one merged launch when both heads go on
+    in fp8 (or both end there), else one launch per head, because a head's LAST hidden layer writes bf16."""
+
+    def __init__(self, folded, device: torch.device):
+        super().__init__(folded, device, hip_gemm=True)
+        conv_w, _, pol_w, pol_b, val_w, val_b = folded
+        c = self.channels
+        perm = lambda wt: wt.reshape(wt.shape[0], c, 42).permute(0, 2, 1).reshape(wt.shape[0], 42 * c)
+        # the BN-folded f32 hidden layers, first layers cell-major like the base's: what is quantised (never the bf16 copies)
+        self._f32_hidden = {"policy": ([perm(pol_w[0].float())] + [w.float() for w in pol_w[1:-1]], [b.float() for b in pol_b[:-1]]),
+                            "value": ([perm(val_w[0].float())] + [w.float() for w in val_w[1:-1]], [b.float() for b in val_b[:-1]])}
+        self.layers = {}        # data_ptr of the bf16 weight tensor linear_relu() is handed -> the layer's fp8 operands
+        self.first = None       # the first layer's launches: [(layer, column range of the merged output or None)]
+        self.fp8_scales = {}    # name of a GEMM input tensor -> its exponent e_x
+
+    def _layer(self, name, w, b, e_in, out_fp8):
+        wq, e_w = quantize_head_weights(w)
+        dq = torch.ldexp(torch.ones(len(e_w), dtype=torch.float64), (-e_in - e_w.to(torch.int64))).float()
+        return {"name": name, "Wq": wq.to(self.device), "e_w": e_w, "dq": dq.to(self.device).contiguous(), "bias": b.float().to(self.device).contiguous(),
+                "e_in": int(e_in), "out_fp8": bool(out_fp8), "e_out": None, "n": int(w.shape[0]), "k": int(w.shape[1])}
+
+    def quantize(self, x, e_x: int):
+        """bf16 [m][k] row view -> e4m3 codes (uint8 [m][k]) of x 2^e_x."""
+        assert x.dtype == torch.bfloat16 and x.stride(1) == 1
+        m, k = x.shape
+        y = torch.empty((m, k), dtype=torch.uint8, device=self.device)
+        check(self.L.c4_quantize_bf16_fp8(x.data_ptr(), y.data_ptr(), m, k, x.stride(0), y.stride(0), float(2.0 ** e_x), _stream(self.device)))
+        return y
+
+    def run_layer(self, ly, x8, out_fp8=None, e_out=None):
+        """One c4_linear_fp8 launch of layer `ly` on the e4m3 rows x8 (out_fp8 / e_out: the calibration's overrides)."""
+        assert x8.dtype == torch.uint8 and x8.stride(1) == 1 and x8.shape[1] == ly["k"]
+        out_fp8 = ly["out_fp8"] if out_fp8 is None else out_fp8
+        e_out = ly["e_out"] if e_out is None else e_out
+        m = x8.shape[0]
+        y = torch.empty((m, ly["n"]), dtype=torch.uint8 if out_fp8 else torch.bfloat16, device=self.device)
+        check(self.L.c4_linear_fp8(x8.data_ptr(), ly["Wq"].data_ptr(), ly["dq"].data_ptr(), ly["bias"].data_ptr(), y.data_ptr(), m, ly["n"], ly["k"],
+                                   x8.stride(0), y.stride(0), 1, 1 if out_fp8 else 0, float(2.0 ** e_out) if out_fp8 else 1.0, 0, _stream(self.device)))
+        return y
+
+    @torch.no_grad()
+    def calibrate(self, net, planes):
+        """Choose every exponent from the calibration rows and build the layers: the input of layer i comes from the fp8 layers in
+        front of it; layer i runs once with bf16 output to observe a_i = max |r|, which sets the e_x of the tensor it writes."""
+        (pw, pb), (vw, vb) = self._f32_hidden["policy"], self._f32_hidden["value"]
+        amax = lambda t: float(t.float().abs().max()) if t.numel() else 0.0
+        feat = net.tower(planes.to(self.device, torch.bfloat16), latency=False)
+        e0 = self.fp8_scales["first"] = activation_exponent(amax(feat))
+        x8 = self.quantize(feat, e0)
+        more_p, more_v = len(pw) > 1, len(vw) > 1
+        f = pw[0].shape[0]
+        if more_p == more_v:    # one merged launch: both halves fp8 (one output tensor, one exponent) or both bf16
+            ly = self._layer("first", torch.cat([pw[0], vw[0]]), torch.cat([pb[0], vb[0]]), e0, more_p)
+            self.first = [(ly, None)]
+            if more_p:
+                ly["e_out"] = self.fp8_scales["policy.1"] = self.fp8_scales["value.1"] = activation_exponent(amax(self.run_layer(ly, x8, out_fp8=False)))
+                h = self.run_layer(ly, x8)
+                p8, v8 = h[:, :f], h[:, f:]
+        else:                   # a head that ends with its first layer takes bf16 from it: one launch per head
+            lp, lv = self._layer("first.policy", pw[0], pb[0], e0, more_p), self._layer("first.value", vw[0], vb[0], e0, more_v)
+            self.first = [(lp, (0, f)), (lv, (f, 2 * f))]
+            for ly, more, key in ((lp, more_p, "policy.1"), (lv, more_v, "value.1")):
+                if more:
+                    ly["e_out"] = self.fp8_scales[key] = activation_exponent(amax(self.run_layer(ly, x8, out_fp8=False)))
+            p8 = self.run_layer(lp, x8) if more_p else None
+            v8 = self.run_layer(lv, x8) if more_v else None
+        for head, ws, bs, bf16_ws, x8 in (("policy", pw, pb, self.pol_w, p8 if more_p else None), ("value", vw, vb, self.val_w, v8 if more_v else None)):
+            for i in range(1, len(ws)):
+                last = i == len(ws) - 1
+                ly = self._layer(f"{head}.{i}", ws[i], bs[i], self.fp8_scales[f"{head}.{i}"], not last)
+                self.layers[bf16_ws[i].data_ptr()] = ly
+                if not last:
+                    ly["e_out"] = self.fp8_scales[f"{head}.{i + 1}"] = activation_exponent(amax(self.run_layer(ly, x8, out_fp8=False)))
+                    x8 = self.run_layer(ly, x8)
+        torch.cuda.synchronize(self.device)
+
+    def first_layer(self, feat):
+        """The tower's bf16 features -> (policy head's, value head's) first hidden activations: e4m3 where the head goes on, bf16
+        where this was its last hidden layer."""
+        x8 = self.quantize(feat, self.fp8_scales["first"])
+        if len(self.first) == 1:
+            h = self.run_layer(self.first[0][0], x8)
+            f = h.shape[1] // 2
+            return h[:, :f], h[:, f:]
+        return self.run_layer(self.first[0][0], x8), self.run_layer(self.first[1][0], x8)
+
+    def linear_relu(self, x, w, b, out=None, config=0):
+        """A further hidden layer (w: the bf16 weight tensor of the base, which names the layer; its tile configuration is not ours)."""
+        return self.run_layer(self.layers[w.data_ptr()], x)
+
+
 class _F32Chain(_TorchChain):
     """c4_conv_tower_f32, c4_linear_f32, c4_head_out_f32 (1 to 64 channels): every product an exact-f32 MFMA fmaf chain in the
     documented order (include/c4a0_hip.h), so a row's outputs depend on that row alone and equal tests/f32_net_ref.c bit for
@@ -346,7 +533,9 @@ class InferenceNet:
     otherwise _TorchChain: PyTorch-ROCm convs + the library GEMM -- a path whose low bits depend on the batch (`batch_invariant`
     False), slower, and never the one the parity suite certifies.  Leaving the hand-written kernels is therefore LOUD:
     `strict=True` refuses (ValueError), the default warns once per construction (EvaluatorFallbackWarning) and `path` says
-    which one runs ("hip" | "torch"; the bench line carries it)."""
+    which one runs ("hip" | "torch"; the bench line carries it).  `head_dtype=torch.float8_e4m3fn` (opt-in) is _Fp8HeadChain: the bf16
+    chain with the heads' hidden layers in OCP FP8 at static, calibrated scales -- `dtype` stays bfloat16 (the planes are), `head_dtype`
+    tells the two apart, and every flag of the bf16 chain (`path`, `batch_invariant`, `graph_safe`, `fused_step_ok`) stays true."""
 
     latency_mode = False  # True while ONE session plays alone on the device (api._play sets it): the narrow layers of a
                           # > 1 024-row batch then use the 128 x 96 tile (12.7 vs 16.8 us alone at 1 700 rows; beside a
@@ -361,15 +550,29 @@ class InferenceNet:
 
     def __init__(self, model: ConnectFourNet, device: torch.device, dtype: torch.dtype = torch.bfloat16,
                  hip_tower: Optional[bool] = None, gemm: Optional[str] = None, gemm_config=None, tower_config: int = 0,
-                 strict: bool = False):
+                 strict: bool = False, head_dtype: Optional[torch.dtype] = None, calibration: Optional[torch.Tensor] = None):
         """gemm: "hip" (the hand-written MFMA GEMM, default with the HIP tower) or "hipblaslt" (PyTorch's library GEMM, an
         A/B switch: its low bits depend on the batch shape).  gemm_config: c4_linear_bf16's tile configuration, one number or
         "wide,narrow" (the merged 2F-wide first layer, the F-wide layers); tower_config: c4_conv_tower_bf16's workgroup
-        shape; 0 / None = automatic.  Measurement switches are constructor arguments: nothing is read from the environment."""
+        shape; 0 / None = automatic.  Measurement switches are constructor arguments: nothing is read from the environment.
+        head_dtype: None (default: today's chain exactly) or torch.float8_e4m3fn -- the heads' hidden layers in OCP FP8 with f32
+        accumulation (_Fp8HeadChain; include/c4a0_hip.h "fp8 hidden layers"), opt-in; its static activation scales are chosen here
+        from `calibration`, a planes tensor [B, 2, 6, 7] (None: calibration_positions(4096, 0)), and readable as `fp8_scales`."""
         self.device, self.dtype = torch.device(device), dtype
         model = model.eval()
         self.channels = model.config.conv_filter_size
         self.n_blocks = len(model.conv) - 1
+        self.head_dtype = head_dtype
+        if head_dtype is not None:
+            if head_dtype != torch.float8_e4m3fn:
+                raise ValueError("head_dtype must be None or torch.float8_e4m3fn")
+            why = ("a HIP device" if self.device.type != "cuda" else "dtype=torch.bfloat16" if dtype != torch.bfloat16 else
+                   "the HIP tower (hip_tower=False was given)" if hip_tower is False else "gemm='hip'" if gemm not in (None, "hip") else
+                   "32 or 64 channels" if self.channels not in (32, 64) else
+                   "both heads with at least one hidden layer" if min(model.config.n_policy_layers, model.config.n_value_layers) < 2 else
+                   "no bf16 tile configuration (gemm_config: c4_linear_fp8 chooses its own)" if gemm_config is not None else None)
+            if why is not None:
+                raise ValueError(f"fp8 hidden layers (head_dtype=torch.float8_e4m3fn) run on the bf16 HIP chain only: they need {why}")
         # f32 networks on the hand-written path only when asked for (hip_tower=True): the f32 chain has no bf16 switches
         f32 = dtype == torch.float32 and bool(hip_tower)
         if f32:
@@ -411,13 +614,25 @@ class InferenceNet:
         self.gemm_config = (int(cfg[0]), int(cfg[-1]))
         self.tower_config = int(tower_config)   # c4_conv_tower_bf16's config, 0 = automatic
         self._np_lock = threading.Lock()   # forward_numpy keeps ONE pinned slot, stream and graph set per net
-        ch = self.chain = (_F32Chain(folded, self.device) if f32 else _Bf16Chain(folded, self.device, hip_gemm=gemm == "hip") if self.hip_tower
-                           else _TorchChain(folded, self.device, dtype))
+        ch = self.chain = (_F32Chain(folded, self.device) if f32 else _Fp8HeadChain(folded, self.device) if head_dtype is not None
+                           else _Bf16Chain(folded, self.device, hip_gemm=gemm == "hip") if self.hip_tower else _TorchChain(folded, self.device, dtype))
         self.merged_w1 = self.merged_b1 = None   # the first hidden layer of BOTH heads as one 2F-wide layer (forward_hidden)
         if len(ch.pol_w) > 1 and len(ch.val_w) > 1:
             self.merged_w1 = torch.cat([ch.pol_w[0], ch.val_w[0]], dim=0).contiguous()
             self.merged_b1 = torch.cat([ch.pol_b[0], ch.val_b[0]], dim=0).contiguous()
             ch.hidden_bias_added(self.merged_b1)
+        if head_dtype is not None:
+            if calibration is None:
+                calibration = torch.from_numpy(positions_to_planes(calibration_positions(4096, 0)))
+            if calibration.dim() != 4 or tuple(calibration.shape[1:]) != (2, N_ROWS, N_COLS) or calibration.shape[0] == 0:
+                raise ValueError("calibration must be a planes tensor [B, 2, 6, 7] with at least one row")
+            ch.calibrate(self, calibration)
+
+    @property
+    def fp8_scales(self) -> Optional[dict]:
+        """fp8 heads: the exponent e_x of every GEMM input tensor by name ("first", "policy.1", "value.1", ...: x8 = q8(x 2^e_x)),
+        a function of (weights, calibration rows) only; None on every other chain."""
+        return dict(self.chain.fp8_scales) if self.head_dtype is not None else None
 
     def __getattr__(self, name):
         if name in InferenceNet._CHAIN_OPERANDS and "chain" in self.__dict__:
@@ -456,9 +671,13 @@ class InferenceNet:
             # session's chain holds an F-wide layer instead of the 2F-wide one: same bits, but every cross-stream edge
             # costs more than the 3.5 us it saves -- the bench halved, 28.0 -> 13.7 k games/s -- and ROCm 7.2's
             # hipStreamEndCapture crashes on a fork from a non-origin stream, tools/capture_nested_fork_repro.py.)
-            h = self._linear_relu(x, self.merged_w1, self.merged_b1, latency=latency)
-            f = self.merged_w1.shape[0] // 2
-            p, v, rest = h[:, :f], h[:, f:], slice(1, -1)
+            if self.head_dtype is not None:   # fp8 heads: quantise, then the first layer in e4m3 (bf16 where a head ends with it)
+                p, v = ch.first_layer(x)
+            else:
+                h = self._linear_relu(x, self.merged_w1, self.merged_b1, latency=latency)
+                f = self.merged_w1.shape[0] // 2
+                p, v = h[:, :f], h[:, f:]
+            rest = slice(1, -1)
         else:   # no merged first layer (a head without hidden layers): the heavy half ends with the tower
             p, v, rest = x, x, slice(0, -1)
         if hook is not None:
@@ -638,6 +857,8 @@ class GroupedNets:
                 return "an evaluator is not a c4a0_amd.nn.InferenceNet"
             if type(ev).forward is not InferenceNet.forward or type(ev).__call__ is not InferenceNet.__call__:
                 return "an evaluator overrides InferenceNet.forward (it must see every evaluation)"
+            if getattr(ev, "head_dtype", None) is not None:
+                return "fp8 hidden layers run through the Python host loop (the grouped chain is bf16)"
         if len(evs) > ROUTE_MAX_MODELS:
             return f"more than {ROUTE_MAX_MODELS} models"
         a = evs[0]

@@ -588,6 +588,46 @@ int c4_sample_move(const uint64_t* game_id_dev, const uint32_t* n_moves_dev, con
  * for c4_linear_bf16's epilogue.  Tower weights and hidden / output weights are bf16.  tests/bf16_ref.py restates the chain in
  * float64 and tests/test_gpu_bf16_exact.py holds the kernels to it bit for bit on data whose every partial sum is exact in f32. */
 
+/* ---- fp8 hidden layers (c4_quantize_bf16_fp8, c4_linear_fp8; opt-in: c4a0_amd/nn.py::InferenceNet(head_dtype=torch.float8_e4m3fn)):
+ * the numerics contract.  tests/fp8_ref.py restates it in float64 with integer arithmetic of its own, tests/test_gpu_fp8_exact.py
+ * holds the kernels to it bit for bit.
+ * Format.  FP8 is OCP e4m3fn: bias 7, largest finite 448, smallest subnormal 2^-9, no infinities, NaN = 0x7F / 0xFF (NOT the fnuz
+ *   format).  q8(v) of an f32 v: NaN -> 0x7F; otherwise clamp to [-448, 448] (an explicit f32 operation in front of the convert
+ *   instruction: no mode bit decides it), then round to nearest, ties to even; subnormals and the sign of zero are kept (a
+ *   negative value that rounds to zero is 0x80).  A NaN is never laundered into a finite value.
+ * Weights (host, at construction; nn.py::quantize_head_weights), from the BN-folded f32 weights (never rounded to bf16 first), the
+ *   first layers in the tower's cell-major order: per output row n, e_w[n] = the largest integer in [-64, 64] with
+ *   max_k |W[n][k]| * 2^e_w[n] <= 448 (an all-zero row: 0); Wq[n][k] = q8(W[n][k] * 2^e_w[n]).  Powers of two: scaling is exact.
+ * Activations: ONE integer exponent per GEMM input tensor, x8 = q8(x * 2^e_x), static, chosen at construction from calibration
+ *   positions and never from the batch: a row's result depends on that row alone.
+ * Layer (c4_linear_fp8):
+ *   1. acc[m][n] = sum_k x8[m][k] * Wq[n][k] in f32 by v_mfma_f32_16x16x128_f8f6f4 (e4m3 x e4m3, no block scales), k ascending in
+ *      128-deep steps (a last step of 64 where k % 128 == 64: the upper half is zeros made in registers; nothing at or beyond
+ *      column k of a row is read), no split-K, no atomics: one fixed order per element whatever m, the row index or `config`;
+ *   2. v = acc * dq[n] + bias[n], dq[n] = 2^(-e_x - e_w[n]) an f32 array, bias f32 as folded: an exact multiply and ONE f32
+ *      rounding in the add (fmaf would give the same value);
+ *   3. r = relu ? (v <= 0 ? +0 : v) : v   (a NaN stays a NaN, -0 becomes +0 under relu);
+ *   4. y = q8(r * out_scale), out_scale = 2^e_x of the consuming layer (exact multiply), or y = bf16(r), round to nearest even.
+ * Chain: c4_conv_tower_bf16 (unchanged, bf16) -> c4_quantize_bf16_fp8 -> the merged 2F-wide first layer (fp8 -> fp8) -> each head's
+ *   further hidden layers (fp8 -> fp8), the LAST hidden layer of each head writing bf16 -> c4_head_out_bf16 or the fused output +
+ *   step launch, unchanged. */
+
+/* y[m][c] = q8(x[m][c] * scale), x bf16 [m][ldx], y e4m3 [m][ldy], c < k; columns k .. ldy - 1 of y are not written.  scale = 2^e_x
+ * (positive, finite).  k % 8 == 0, ldx % 8 == 0, ldy % 8 == 0, x_dev 16-byte and y_dev 8-byte aligned (a thread moves 8 elements:
+ * a 16-byte load, an 8-byte store).  No synchronisation: capturable. */
+int c4_quantize_bf16_fp8(const void* x_dev /*bf16 [m][ldx]*/, void* y_dev /*fp8 [m][ldy]*/, uint32_t m, uint32_t k,
+                         uint32_t ldx, uint32_t ldy, float scale /*2^e_x*/, void* stream);
+/* One fp8 hidden layer, see the contract above.  n % 192 == 0, k % 64 == 0; ldx >= k, ldx % 16 == 0, x8_dev and w8_dev 16-byte
+ * aligned (rows are read 16 bytes at a time; x8 may be a column view of a wider tensor: nothing at or beyond column k of a row is
+ * read); ldy >= n (in elements of the output type), ldy % 4 == 0, y_dev 4-byte (fp8) or 8-byte (bf16) aligned; dq_dev and bias_dev
+ * 16-byte aligned; m at most 65 535 * 64.  out_fp8 != 0: y is e4m3 = q8(r * out_scale), out_scale positive and finite; else y is
+ * bf16 and out_scale is ignored.  config: 0 = automatic; 3 / 4 = operands staged through LDS, 128 x 192 / 64 x 192 tiles (the automatic
+ * choices); 1 / 2 = fragments read straight from global memory, 64- / 128-row tiles (measured alternatives); all compute the same
+ * bits.  x8 and w8 below 4 GiB each.  No synchronisation: capturable.  Bad arguments: C4_ERR_BAD_ARG and a c4_last_error_string. */
+int c4_linear_fp8(const void* x8_dev /*[m][ldx]*/, const void* w8_dev /*[n][k]*/, const float* dq_dev /*[n]*/, const float* bias_dev /*[n]*/,
+                  void* y_dev /*fp8 or bf16 [m][ldy]*/, uint32_t m, uint32_t n, uint32_t k, uint32_t ldx, uint32_t ldy,
+                  uint32_t relu, uint32_t out_fp8, float out_scale, uint32_t config, void* stream);
+
 /* ---- evaluator building block: the residual conv tower of ConnectFourNet (src/c4a0/nn.py:64-70,
  * 184-195; eval-mode BatchNorm folded into the second conv of each block) as one MFMA kernel.
  *   planes_dev bf16 [n_boards][2][6][7] (what c4_session_step writes with planes_dtype = 1)
