@@ -25,6 +25,8 @@ FLAG_HOLD = 32            # include/c4a0_hip.h C4_FLAG_HOLD: every request is on
 HOLD_PARKED = 64          # ... the slot status of a parked game
 HOLD_MOVE_NONE, HOLD_MOVE_SAMPLE = -1, -2   # c4_session_hold_resume: a slot's move (or a column 0..6) ...
 HOLD_OK, HOLD_REFUSED_TERMINAL, HOLD_REFUSED_COLUMN, HOLD_REFUSED_UNSEARCHED, HOLD_REFUSED_SAMPLE, HOLD_NO_GAME = range(6)   # ... and its result
+HOLD_UNDO_NONE, HOLD_UNDO_ONE, HOLD_UNDO_ALL = 0, 1, 2   # c4_session_hold_undo: what a slot takes back (MctsGame::undo_move / reset_game) ...
+HOLD_REFUSED_NO_MOVES, HOLD_REFUSED_REQUEST = 6, 7     # ... and the two results it adds: no move made yet, not one of the three requests
 HOLD_POLL_UNKNOWN = 0xFFFFFFFF
 MAX_SAMPLES_PER_GAME = 43
 ROUTE_MAX_MODELS = 32     # include/c4a0_hip.h C4_ROUTE_MAX_MODELS: models one routed batch (c4_session_route_leaves) may hold
@@ -137,6 +139,7 @@ SIGNATURES = {
     "c4_session_route_leaves": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
     "c4_session_set_iterations": (C.c_int, [_vp, C.c_uint32]),
     "c4_session_hold_resume": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "c4_session_hold_undo": (C.c_int, [_vp, _vp, _vp]),
     "c4_session_snapshot": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64]),
     "c4_session_hold_poll": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "c4_session_leaves": (C.c_int, [_vp, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint32), _P(C.c_uint32)]),

@@ -1159,10 +1159,12 @@ static int launch_step(c4_session* s, const uint32_t* inverse, const float* answ
   return maybe_reclaim(s);
 }
 
-// One per-slot array of c4_session_hold_resume as the kernel may use it: device memory and pinned host memory through
+}  // namespace
+
+// One per-slot array of c4_session_hold_resume / c4_session_hold_undo as the kernel may use it: device memory and pinned host memory through
 // device_view; pageable host memory (what HIP does not know) through the session's staging buffer `stage` (copied in now when
 // `copy_in`).  *staged tells the caller which.
-static int hold_array(c4_session* s, const void* ptr, void** stage, bool copy_in, const char* what, void** out, bool* staged) {
+int hold_array(c4_session* s, const void* ptr, void** stage, bool copy_in, const char* what, void** out, bool* staged) {
   const size_t bytes = (size_t)s->cfg.n_slots * 4;
   *staged = false;
   hipPointerAttribute_t attr{};
@@ -1175,8 +1177,6 @@ static int hold_array(c4_session* s, const void* ptr, void** stage, bool copy_in
   *staged = true;
   return C4_OK;
 }
-
-}  // namespace
 
 int c4host::fail(int code, const std::string& msg) {
   g_last_error = msg;

@@ -64,6 +64,7 @@ struct c4_session {
 #define C4_INTERNAL __attribute__((visibility("hidden")))   // crosses files, not the library's boundary
 C4_INTERNAL int maybe_reclaim(c4_session* s);                                                  // c4_session_maint.hip
 C4_INTERNAL int device_view(const void* ptr, int device, const char* what, void** out);        // c4_session_callback.hip
+C4_INTERNAL int hold_array(c4_session* s, const void* ptr, void** stage, bool copy_in, const char* what, void** out, bool* staged);   // c4_session.hip
 
 namespace {
 

@@ -1,5 +1,6 @@
-// c4_session_maint.hip -- what keeps a running session's memory in shape between steps: tail compaction (c4_session_compact)
-// and the reclaimed arenas (C4_FLAG_RECLAIM: k_arena_reclaim behind every reclaim_period-th step launch).
+// c4_session_maint.hip -- what keeps a running session's memory in shape between steps: tail compaction (c4_session_compact),
+// the reclaimed arenas (C4_FLAG_RECLAIM: k_arena_reclaim behind every reclaim_period-th step launch) and a hold session's undo
+// (c4_session_hold_undo: k_hold_undo in front of the resume launch).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -173,6 +174,58 @@ __global__ __launch_bounds__(kReclaimThreads) void k_arena_reclaim(Params p, uin
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Hold sessions (C4_FLAG_HOLD): MctsGame::undo_move (mcts.rs:230-245) / reset_game (mcts.rs:225-227) for every slot, 8 lanes per
+// game like the step.  The reference pops the last RecordedMove (or all of them) and makes the root a FRESH node at the popped
+// move's position -- Node::new(pos, Weak::new(), 1.0): the whole tree is dropped.  That position is in the game's own row of the
+// sample store: record k was written when move k was made and holds the position it was made from.  The slot gets what reset_slot
+// gives a new game there (block 0 = the root's own entry with prior 1.0, bump pointer at 1, leaf = root, terminal state 0: a move
+// was made from that position), with game_id and ordinal its own and the state word carrying the shortened move count, and is left
+// PARKED: the resume launch that follows (c4_session_hold_undo) is the one place where a game becomes active, and it selects the
+// root as the pending leaf.  A finished game's finish is reversed: sample count 0, games_done and samples down by its share (the
+// wavefront's counter row takes the negative amounts: the host's sum is modulo 2^64).  Records past the new count and the q
+// values of the remaining ones stay as they are: the next finish rewrites them.  A refused slot is not written at all.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_hold_undo(Params p, const int32_t* __restrict__ requests, int32_t* __restrict__ results) {
+  const uint32_t lane = threadIdx.x & 63, sub = lane & 7;
+  const uint32_t g = blockIdx.x * kGamesPerWave + (lane >> 3);
+  if (g >= p.n_slots) return;
+  Slot* st = p.slots + g;
+  const int32_t req = requests[g];
+  const uint32_t state = st->state, ordinal = st->ordinal;
+  const uint32_t status = slot_status(state), n_moves = (state >> 16) & 0xFFu;
+  int32_t res = C4_HOLD_OK;
+  if (req == C4_HOLD_UNDO_NONE) res = C4_HOLD_OK;
+  else if (req != C4_HOLD_UNDO_ONE && req != C4_HOLD_UNDO_ALL) res = C4_HOLD_REFUSED_REQUEST;
+  else if (status != kActive && status != kParked) res = C4_HOLD_NO_GAME;      // idle, or ended by a device error
+  else if (n_moves == 0) res = C4_HOLD_REFUSED_NO_MOVES;                       // undo_move returns false (mcts.rs:231)
+  if (sub == 0 && results) results[g] = res;
+  if (req == C4_HOLD_UNDO_NONE || res != C4_HOLD_OK) return;
+  const uint32_t new_count = req == C4_HOLD_UNDO_ONE ? n_moves - 1u : 0u;
+  const c4_sample_rec* rec = p.samples + (size_t)ordinal * C4_MAX_SAMPLES_PER_GAME + new_count;
+  const uint64_t m = rec->mask, v = rec->value;
+  const uint32_t contributed = p.sample_counts[ordinal];                      // != 0: the game is finished
+  // every lane has read the state line before lane 0 rewrites it (one wavefront, program order)
+  Block* blocks = p.blocks + (size_t)g * p.blocks_per_slot;
+  reinterpret_cast<uint4*>(blocks)[sub] = make_uint4(0, 0, 0, sub == 0 ? __float_as_uint(1.0f) : 0u);
+  if (sub == 0) {
+    st->root_mask = m; st->root_value = v;
+    st->leaf_mask = m; st->leaf_value = v;
+    st->root_n = 0;
+    st->state = slot_state(kParked, 0, new_count, 0, 0);
+    st->arena = 1;            // n_blocks = 1, root not expanded: the arena is given back
+    st->root_ref = 0;
+    st->path[0] = 0;
+    if (status == kActive) atomicAdd(&p.glob->hold_active, 0xFFFFFFFFu);       // (the resume launch counts it again)
+    if (contributed) {
+      p.sample_counts[ordinal] = 0;
+      atomicAdd(&p.glob->games_done, ~0ull);
+      atomicAdd(&p.wave_ctr[(size_t)blockIdx.x * CTR_N + CTR_DONE], ~0ull);
+      atomicAdd(&p.wave_ctr[(size_t)blockIdx.x * CTR_N + CTR_SAMPLES], 0ull - (unsigned long long)contributed);
+    }
+  }
+}
+
 }  // namespace
 
 // Called behind every step launch of a reclaimed session: every `period`-th launch is followed by k_arena_reclaim on the same
@@ -232,6 +285,25 @@ int c4_session_compact(c4_session* s, uint32_t multiple, uint32_t* n_active, uin
   }
   if (n_active) *n_active = plan.n_active;
   if (n_slots_now) *n_slots_now = s->p.n_slots;
+  return C4_OK;
+}
+
+int c4_session_hold_undo(c4_session* s, const int32_t* requests, int32_t* results) {
+  if (!s) return fail(C4_ERR_BAD_ARG, "null session");
+  if (!hold_mode(s)) return fail(C4_ERR_BAD_ARG, "c4_session_hold_undo: not a hold session (C4_FLAG_HOLD)");
+  if (!requests) return fail(C4_ERR_BAD_ARG, "c4_session_hold_undo: requests is NULL (one C4_HOLD_UNDO_* per slot of the C4_FLAG_HOLD session)");
+  if (!s->bound || !s->have_games) return fail(C4_ERR_NOT_BOUND, "bind_io and set_games must precede c4_session_hold_undo");
+  C4_ON_DEVICE(s->cfg.device);
+  void *q = nullptr, *r = nullptr;
+  bool sq = false, sr = false;
+  if (int rc = hold_array(s, requests, (void**)&s->hold_cols_dev, true, "c4_session_hold_undo: requests", &q, &sq)) return rc;
+  if (results) if (int rc = hold_array(s, results, (void**)&s->hold_results_dev, false, "c4_session_hold_undo: results", &r, &sr)) return rc;
+  hipLaunchKernelGGL(k_hold_undo, dim3((s->p.n_slots + kGamesPerWave - 1) / kGamesPerWave), dim3(64), 0, s->stream, s->p, (const int32_t*)q, (int32_t*)r);
+  HIP_TRY(hipGetLastError());
+  // ensure_bg_thread for every slot: the undone games select their root and become active, the others park or go on as they are
+  if (int rc = c4_session_hold_resume(s, nullptr, nullptr, nullptr)) return rc;
+  if (sr) HIP_TRY(hipMemcpyAsync(results, r, (size_t)s->cfg.n_slots * 4, hipMemcpyDeviceToHost, s->stream));
+  if (sq || sr) HIP_TRY(hipStreamSynchronize(s->stream));   // pageable host memory: the caller's arrays are done with when the call returns
   return C4_OK;
 }
 

@@ -2,7 +2,8 @@
 
 The reference's `InteractivePlay` (rust/src/interactive_play.rs, the engine behind `run_tui`) is ONE `MctsGame` whose tree lives on:
 searched up to a visit budget, moved by `make_move` / `make_random_move(temperature)` with the subtree under the move kept
-(mcts.rs:187-206), its budget raised by `increase_mcts_iters`, read by `snapshot()`.  `Engine` is that for P games at once on a hold
+(mcts.rs:187-206), taken back by `undo_move` / `reset_game` (mcts.rs:225-245), its budget raised by `increase_mcts_iters`, read by
+`snapshot()`.  `Engine` is that for P games at once on a hold
 session (include/c4a0_hip.h C4_FLAG_HOLD): game i lives on slot i, every operation is one launch for all of them, and nothing but
 the moves, the move results and the snapshots crosses to the host.  It plays matches against an outside engine or a person, or
 suites of games move by move under host control; finished games come out as the `PlayGamesResult` self-play produces.
@@ -92,7 +93,7 @@ class Engine:
             raise
         self._graph, self._graph_target = None, None
         self.rounds = 0            # lock-step rounds of the last search()
-        self.last_results = np.zeros(self.n_games, dtype=np.int32)   # c4_session_hold_resume's codes of the last move call
+        self.last_results = np.zeros(self.n_games, dtype=np.int32)   # c4_session_hold_resume's / _hold_undo's codes of the last move / undo call
 
     # ---------------------------------------------------------------- lifetime
     def close(self):
@@ -209,6 +210,31 @@ class Engine:
             raise ValueError("one flag per game")
         temps = np.broadcast_to(np.asarray(temperature, dtype=np.float32), (self.n_games,))
         return self._move(np.where(sel, _lib.HOLD_MOVE_SAMPLE, _lib.HOLD_MOVE_NONE), temps)
+
+    # ---------------------------------------------------------------- taking moves back
+    def _undo(self, request: int, where) -> np.ndarray:
+        sel = np.ones(self.n_games, dtype=bool) if where is None else np.asarray(where, dtype=bool).reshape(-1)
+        if len(sel) != self.n_games:
+            raise ValueError("one flag per game")
+        self._cols.copy_(torch.from_numpy(np.where(sel, request, _lib.HOLD_UNDO_NONE).astype(np.int32)))
+        self.session.hold_undo(self._cols, self._results)
+        self.last_results = self._results.cpu().numpy().astype(np.int32)   # (synchronises)
+        return (self.last_results == _lib.HOLD_OK) & sel
+
+    def undo_moves(self, where=None) -> np.ndarray:
+        """InteractivePlay::undo_move (MctsGame::undo_move, mcts.rs:230-245) for the games `where` selects (bool[P]; None = all):
+        the last move is taken back.  Returns bool[P]: a move was undone; a game that has made no move is refused
+        (`last_results`: c4a0_amd._lib.HOLD_REFUSED_NO_MOVES) and stays exactly as it was.  As in the reference the root is a
+        FRESH node at the earlier position -- the tree is dropped, the game's arena given back, the next sampled move's seed uses
+        the shortened move count -- and is the game's pending leaf: search() searches it towards the target again.  A finished
+        game can be undone like any other; it leaves result() until a move finishes it again."""
+        return self._undo(_lib.HOLD_UNDO_ONE, where)
+
+    def reset_games(self, where=None) -> np.ndarray:
+        """InteractivePlay::reset_game (MctsGame::reset_game, mcts.rs:225-227: undo_move until it returns false) for the games
+        `where` selects: back to the start position with a fresh root and no moves.  Returns bool[P]: something was undone; a
+        game without moves keeps its tree (`last_results`: HOLD_REFUSED_NO_MOVES)."""
+        return self._undo(_lib.HOLD_UNDO_ALL, where)
 
     # ---------------------------------------------------------------- reading
     def snapshot(self, player0_perspective: bool = False) -> Snapshot:

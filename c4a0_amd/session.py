@@ -323,6 +323,14 @@ class DeviceSession:
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         check(self.L.c4_session_hold_resume(self._h, ptr(cols), ptr(temperatures), ptr(results)))
 
+    def hold_undo(self, requests: torch.Tensor, results: Optional[torch.Tensor] = None):
+        """c4_session_hold_undo: per slot what to take back (int32[n_slots]: c4a0_amd._lib.HOLD_UNDO_NONE, _ONE the last move,
+        _ALL every move), then what hold_resume() does for every slot; results int32[n_slots] receives the per-slot codes
+        (HOLD_OK, HOLD_NO_GAME, HOLD_REFUSED_NO_MOVES, HOLD_REFUSED_REQUEST).  An undone game has a fresh root -- no visits, no
+        tree, its arena given back -- as its pending leaf.  Device tensors, as hold_resume takes them.  Asynchronous."""
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(self.L.c4_session_hold_undo(self._h, ptr(requests), ptr(results)))
+
     def snapshot(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """c4_session_snapshot: (records SAMPLE_DTYPE[n_slots], root visit counts uint32[n_slots], slot status uint32[n_slots])."""
         recs = np.zeros(self.n_slots, dtype=SAMPLE_DTYPE)

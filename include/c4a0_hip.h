@@ -139,6 +139,9 @@ typedef struct {
                                  and, when the new root is terminal, completes the game's records as a finished self-play game's (to_result's q
                                  signs, the uniform terminal sample, sample count; counted in games_done): c4_session_sample_counts /
                                  _drain_samples / _pack_samples deliver finished games only, unchanged.  ref_skipped_sims stays 0.
+                                 Taking moves back: c4_session_hold_undo (MctsGame::undo_move / reset_game) makes the root a FRESH node at the
+                                 position an earlier move was made from -- the tree is dropped, the arena's bump pointer restarts -- and takes
+                                 a finished game out of the records and out of games_done / samples again.
                                  Arena: 43 n + 8 blocks per slot by default, n the creation-time n_mcts_iterations (a root gets at most n new
                                  simulations, a game has at most 42 roots), never reclaimed -- above n = 1 523 pass blocks_per_slot;
                                  C4_ERR_ARENA_OVERFLOW stays the per-slot outcome of exhaustion.
@@ -158,6 +161,13 @@ typedef struct {
 #define C4_HOLD_REFUSED_UNSEARCHED 3  /* the root has no children yet: not one simulation since it became the root (the reference panics, mcts.rs:196) */
 #define C4_HOLD_REFUSED_SAMPLE 4      /* the sampled column is not legal (mcts.rs:196-200 panics; only while the root's children have no visits) */
 #define C4_HOLD_NO_GAME 5             /* the slot holds no live game: never given one, or ended by a device error */
+/* c4_session_hold_undo: what a slot is asked to take back ... */
+#define C4_HOLD_UNDO_NONE 0      /* nothing */
+#define C4_HOLD_UNDO_ONE 1       /* MctsGame::undo_move (mcts.rs:230-245): the last move */
+#define C4_HOLD_UNDO_ALL 2       /* MctsGame::reset_game (mcts.rs:225-227): every move */
+/* ... and the two results it adds to C4_HOLD_OK and C4_HOLD_NO_GAME */
+#define C4_HOLD_REFUSED_NO_MOVES 6    /* the game has made no move (undo_move returns false; reset_game does nothing) */
+#define C4_HOLD_REFUSED_REQUEST 7     /* requests[slot] is none of the three codes above */
 #define C4_HOLD_POLL_UNKNOWN 0xFFFFFFFFu /* c4_session_hold_poll: no probe enqueued since the last resume has landed yet */
 
 /* Device-side counters (the reference's progress bars, self_play.rs:352-381, plus the
@@ -530,6 +540,23 @@ int c4_session_set_iterations(c4_session* s, uint32_t n_mcts_iterations);
  * memory (then the call copies and synchronises the stream); device or pinned arrays must stay untouched until the stream has passed
  * the launch.  The reference's panics stay errors of the slot: C4_ERR_DEGENERATE_POLICY from a sampled move's weights. */
 int c4_session_hold_resume(c4_session* s, const int32_t* cols, const float* temperatures, int32_t* results);
+/* InteractivePlay::undo_move / reset_game (interactive_play.rs; MctsGame::undo_move, mcts.rs:230-245, reset_game = undo_move until it
+ * returns false, mcts.rs:225-227) + ensure_bg_thread for every slot, stream-ordered on the session's stream: per slot requests[slot]
+ * (C4_HOLD_UNDO_NONE, _ONE or _ALL).  results[slot]: C4_HOLD_OK (accepted, or none asked); C4_HOLD_REFUSED_REQUEST for any other
+ * request value; C4_HOLD_NO_GAME for a slot without a live game; C4_HOLD_REFUSED_NO_MOVES for a game that has made no move -- a game
+ * finished at its start by a terminal start position among them, which keeps its one sample.  A refused slot stays byte for byte as
+ * it was, pending leaf and evaluator row included.  An ACCEPTED undo leaves the game with moves - 1 (ONE) or 0 (ALL) moves made and,
+ * as the reference does, a FRESH root (Node::new(pos, Weak::new(), 1.0): no visits, no children, leaf = root) at the position that
+ * move was made from, read from the game's own row of the sample store (the record of that move); the whole tree is dropped, so the
+ * slot's arena starts again at block 1.  game_id and ordinal stay; the seed of the next sampled move uses the shortened move count.
+ * If the game was finished, the finish is reversed: its sample count is 0 again (c4_session_sample_counts / _drain_samples /
+ * _pack_samples no longer deliver it) and the session's games_done and samples counters (c4_session_counters, c4_session_poll) drop
+ * by the game's share.  Records past the new move count, and the q values of the remaining ones, are stale until the next finish
+ * rewrites them.  Then every slot does what c4_session_hold_resume(s, NULL, NULL, NULL) does: an undone game selects its root as
+ * the pending leaf and is active.  No argument of a captured launch changes: HIP graphs captured earlier stay valid.
+ * The arrays follow c4_session_hold_resume's rules (n_slots entries; device, pinned or ordinary host memory -- then the call copies
+ * and synchronises the stream); results may be NULL.  requests == NULL or a session without C4_FLAG_HOLD: C4_ERR_BAD_ARG. */
+int c4_session_hold_undo(c4_session* s, const int32_t* requests, int32_t* results);
 /* InteractivePlay::snapshot (interactive_play.rs:57, 145-166) of every slot, ONE launch and ONE copy: dst_host[slot] = (game_id, the
  * root position, root_policy (mcts.rs:396-412), the root's q_sum / (visits + 1) (mcts.rs:359-367; the arithmetic of
  * c4_session_root_stats), meta = moves made | 3 << 16), visits_host[slot] = the root's visit count, status_host[slot] = 0 idle (no
