@@ -17,6 +17,9 @@ def __getattr__(name):  # torch / the HIP library are loaded on first use of the
     if name == "Engine":   # GPU-resident interactive play: games whose trees persist across moves from outside
         from .engine import Engine
         return Engine
+    if name in ("Solver", "SolveResult", "SolverScore"):   # exact solver on the GPU: solve / score_policies, and solver_score of results
+        from . import solver
+        return getattr(solver, name)
     if name == "SearchResult":
         from .results import SearchResult
         return SearchResult

@@ -91,6 +91,17 @@ class PlayPhases(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SolverStats(C.Structure):
+    """include/c4a0_hip.h c4_solver_stats."""
+    _fields_ = [(n, C.c_uint64) for n in ("nodes", "probes", "launches", "tasks", "unsolved_tasks")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+SOLVE_FULL_COLUMN, SOLVE_UNSOLVED = -1000, -32768   # include/c4a0_hip.h C4_SOLVE_FULL_COLUMN, C4_SOLVE_UNSOLVED
+SOLVER_TT_ENTRIES = 1 << 24                         # C4_SOLVER_TT_ENTRIES
+
 # every symbol include/c4a0_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -165,6 +176,9 @@ SIGNATURES = {
     "c4_quantize_bf16_fp8": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _vp]),
     "c4_linear_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                 C.c_uint32, _vp]),
+    "c4_solver_create": (C.c_int, [C.c_uint64, C.c_int32, _P(_vp)]),
+    "c4_solver_destroy": (C.c_int, [_vp]),
+    "c4_solver_solve": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _P(SolverStats), _vp]),
 }
 
 _lib = None

@@ -317,8 +317,9 @@ def _ids_table(reqs) -> np.ndarray:
 
 
 class PlayGamesResult:
-    """pybridge.rs:58-158.  `score_policies` needs the external PascalPons solver and the
-    rocksdb cache (rust/src/solver.rs) -- out of scope, raises NotImplementedError."""
+    """pybridge.rs:58-158.  `score_policies` takes the paths of the external PascalPons solver, its book and a rocksdb
+    cache (rust/src/solver.rs), which mean nothing here: it raises NotImplementedError.  The same number comes from
+    `solver_score`, on the GPU solver (c4a0_amd/solver.py)."""
 
     def __init__(self, results: Iterable[GameResult] = ()):  # pybridge.rs:67-70: empty constructor for unpickling
         self._results: List[GameResult] = list(results)
@@ -473,7 +474,19 @@ class PlayGamesResult:
         return samples[:cut], samples[cut:]
 
     def score_policies(self, solver_path: str, solver_book_path: str, solution_cache_path: str) -> float:
-        raise NotImplementedError("score_policies needs the external c4solver binary and book (reference rust/src/solver.rs); out of scope")
+        raise NotImplementedError("score_policies needs the external c4solver binary and book (reference rust/src/solver.rs); out of scope. "
+                                  "The GPU solver gives the same measure without them: PlayGamesResult.solver_score(solver=None, min_stones=0)")
+
+    def solver_score(self, solver=None, *, min_stones: int = 0, **budget):
+        """What the reference's `score_policies` measures (pybridge.rs:129-147, stored as TrainingGen.solver_score), on the GPU
+        solver: a SolverScore (score, n_scored, n_unsolved, n_skipped).  score = the mean, over the non-terminal samples with at
+        least `min_stones` stones that the solver finished within its budget, of 1.0 where the policy's first maximum is a best
+        move, 0.5 where it is a winning move that is not best, 0.0 otherwise; NaN when there are none.  It IS the reference's
+        number when n_unsolved == 0 and min_stones == 0.  `solver`: a c4a0_amd.Solver (None: one is made for the call);
+        `budget`: nodes_per_launch / max_nodes_per_position of Solver.solve.  Works on the packed records; builds no Sample."""
+        from .solver import solver_score_of_records
+
+        return solver_score_of_records(self._tables()[1], solver, min_stones=min_stones, **budget)
 
     def unique_positions(self) -> int:  # pybridge.rs:150-157
         if self._lazy is not None:
@@ -570,6 +583,13 @@ class SearchResult:
     def best_moves(self) -> np.ndarray:
         """int64[P]: the column of each policy's maximum, the FIRST one among equals, as Solution::score_policy picks it."""
         return np.argmax(self.records["policy"], axis=1).astype(np.int64) if len(self.records) else np.zeros(0, dtype=np.int64)
+
+    def solver_score(self, solver=None, *, min_stones: int = 0, **budget):
+        """PlayGamesResult.solver_score for the searched positions: how often the root policy's first maximum is a best (1.0)
+        or a winning (0.5) move according to the GPU solver -- a SolverScore (score, n_scored, n_unsolved, n_skipped)."""
+        from .solver import solver_score_of_records
+
+        return solver_score_of_records(self.records, solver, min_stones=min_stones, **budget)
 
     def samples(self) -> List[Sample]:
         """One Sample (types.rs:103-110) per position: (pos, root policy, root q_penalty, root q_no_penalty)."""

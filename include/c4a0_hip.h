@@ -783,6 +783,49 @@ int c4_head_out_f32(const float* hidden_policy_dev, const float* hidden_value_de
                     const float* b_policy_dev, const float* b_value_dev, uint32_t n_boards, uint32_t policy_features, uint32_t value_features,
                     uint32_t policy_row_stride, uint32_t value_row_stride, float* logprobs, float* q, float* preact, void* stream);
 
+/* ---- exact solver ----------------------------------------------------------------------------------------------------------
+ * What the reference gets from Pascal Pons' c4solver binary, its opening book and a rocksdb cache (rust/src/solver.rs): here a HIP
+ * alpha-beta search with no binary, no book and no database.  These calls only ADD functions: C4_ABI_VERSION stays what it was.
+ *
+ * For a non-terminal position with s stones, scores[c] is what `c4solver -a` prints and solver.rs:167-172 reads as a Solution:
+ *   a full column                      C4_SOLVE_FULL_COLUMN (-1000)
+ *   a move that wins at once           (43 - s) / 2
+ *   any other move                     -score(the position after it)
+ * score(q) = the exact negamax value: +k if the side to move wins with its (22 - k)-th stone, 0 for a draw, -k symmetrically.
+ *
+ * Every legal child that is not answered at once is one task; one GPU lane searches one task (null-window alpha-beta, explicit stack)
+ * against ONE lossy transposition table in device memory shared by all lanes and kept by the handle across calls (the role of the
+ * reference's CachingSolver).  An entry is one aligned 64-bit word (49-bit key, 8-bit bound) read and written whole, so concurrent
+ * writers change how many nodes are visited, never a score.  Nothing runs unbounded: a launch gives every lane nodes_per_launch node
+ * visits (a visit = a node whose moves are generated; children answered at once by the rules, the window or the table belong to
+ * their parent's visit); a task unfinished then keeps its stack (320 bytes, in device memory for the length of the call) and goes on in
+ * the next launch; a task that has used max_nodes_per_position visits is given up.  A position with a task given up is returned with
+ * solved = 0 and seven C4_SOLVE_UNSOLVED.  There is no opening book, so positions with few stones end there: the limit of this solver, not an error. */
+#define C4_SOLVE_FULL_COLUMN (-1000)
+#define C4_SOLVE_UNSOLVED (-32768)                    /* INT16_MIN */
+#define C4_SOLVER_TT_ENTRIES (1ull << 24)             /* the default table: 2^24 entries = 128 MB */
+#define C4_SOLVER_NODES_PER_LAUNCH 3072ull            /* the defaults that 0 selects: a launch of ~50 ms with every lane busy, and ~10 s for */
+#define C4_SOLVER_MAX_NODES_PER_POSITION (1ull << 20) /* a position that ends unsolved (measured: DESIGN.md section 3, profiles/solver_rate.json) */
+typedef struct c4_solver c4_solver;
+typedef struct {
+  uint64_t nodes;          /* node visits (expanded nodes), the unit of both budgets */
+  uint64_t probes;         /* all nodes entered, the answered-at-once ones included */
+  uint64_t launches;
+  uint64_t tasks;
+  uint64_t unsolved_tasks; /* tasks given up at max_nodes_per_position */
+} c4_solver_stats;
+
+/* A solver on `device` with a table of tt_entries entries (a power of two, 16 .. 2^32; 8 bytes each), zeroed. */
+int c4_solver_create(uint64_t tt_entries, int32_t device, c4_solver** out);
+int c4_solver_destroy(c4_solver* handle);
+/* positions_host: uint64 [n_positions][2] (mask, value) as everywhere (bit = 7 row + col), each non-terminal and well formed --
+ * C4_ERR_BAD_ARG names the first that is not.  scores_out int16 [n_positions][7], solved_out uint8 [n_positions], stats_out (may be
+ * NULL): host memory.  nodes_per_launch / max_nodes_per_position: 0 = the defaults above.  The work runs on `stream`; the call waits
+ * for that stream only and returns when the answer is in the host arrays.  n_positions == 0 is answered without touching the device.
+ * One call at a time per handle (others wait). */
+int c4_solver_solve(c4_solver* handle, const uint64_t* positions_host, uint64_t n_positions, uint64_t nodes_per_launch,
+                    uint64_t max_nodes_per_position, int16_t* scores_out, uint8_t* solved_out, c4_solver_stats* stats_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
