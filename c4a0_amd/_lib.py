@@ -99,6 +99,20 @@ class SolverStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class SolverStatsEx(C.Structure):
+    """include/c4a0_hip.h c4_solver_stats_ex."""
+    _fields_ = [(n, C.c_uint64) for n in ("nodes", "probes", "launches", "tasks", "unsolved_tasks", "split_tasks", "combined_nodes",
+                                          "dropped_tasks", "book_hits_host", "book_inserts", "book_full")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class SolverOptions(C.Structure):
+    """include/c4a0_hip.h c4_solver_options."""
+    _fields_ = [(n, C.c_uint64) for n in ("struct_size", "nodes_per_launch", "max_nodes_per_position", "split_stones", "split_max_tasks")]
+
+
 SOLVE_FULL_COLUMN, SOLVE_UNSOLVED = -1000, -32768   # include/c4a0_hip.h C4_SOLVE_FULL_COLUMN, C4_SOLVE_UNSOLVED
 SOLVER_TT_ENTRIES = 1 << 24                         # C4_SOLVER_TT_ENTRIES
 
@@ -179,6 +193,10 @@ SIGNATURES = {
     "c4_solver_create": (C.c_int, [C.c_uint64, C.c_int32, _P(_vp)]),
     "c4_solver_destroy": (C.c_int, [_vp]),
     "c4_solver_solve": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _P(SolverStats), _vp]),
+    "c4_solver_create_ex": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _P(_vp)]),
+    "c4_solver_solve_ex": (C.c_int, [_vp, _vp, C.c_uint64, _P(SolverOptions), _vp, _vp, _P(SolverStatsEx), _vp]),
+    "c4_solver_book_export": (C.c_int, [_vp, _vp, C.c_uint64, _P(C.c_uint64)]),
+    "c4_solver_book_import": (C.c_int, [_vp, _vp, C.c_uint64]),
 }
 
 _lib = None

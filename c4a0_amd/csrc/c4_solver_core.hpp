@@ -9,6 +9,7 @@
 // The search is the published alpha-beta solver of Pascal Pons (blog.gamesolver.org): negamax on null windows that narrow
 // [lo, hi] at the root, non-losing moves only, centre-first move order refined by the number of winning cells a move opens, a
 // lossy transposition table of bounds.  Scores are his: +k = the side to move wins with its (22 - k)-th stone, 0 = draw.
+// Beside the table a search may read a book: exact scores under canonical keys, written by the host only (c4_solver_split.hpp).
 //
 // A lane keeps an explicit stack of at most kMaxDepth frames of two 32-bit words (the caller gives the memory: LDS on the
 // device) and advances ONE node per call of step(): lanes of a wavefront that search different trees run the same code.
@@ -91,6 +92,31 @@ C4S_HD uint64_t non_losing_moves(uint64_t pos, uint64_t mask) {
 
 C4S_HD uint64_t tt_index(uint64_t key, uint32_t log2_entries) { return (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_entries); }
 
+// The book (c4_solver_split.hpp): a lossless open-addressed table of exact scores that only the host writes, between launches.
+// An entry = canonical key (49 bits) | (score + kUpperBias) << 56; 0 = empty.  The canonical key is the smaller of pos + mask and
+// the same of the mirror image: the sum is carry-free per column, so reversing the seven 7-bit columns of the key mirrors it.
+C4S_HD uint64_t mirror_columns(uint64_t x) {
+  const uint64_t c = 0x7Full;
+  return ((x & c) << 42) | ((x & (c << 7)) << 28) | ((x & (c << 14)) << 14) | (x & (c << 21)) | ((x >> 14) & (c << 14)) | ((x >> 28) & (c << 7)) |
+         ((x >> 42) & c);
+}
+C4S_HD uint64_t canonical_key(uint64_t pos, uint64_t mask) {
+  const uint64_t k = pos + mask, m = mirror_columns(k);
+  return k < m ? k : m;
+}
+// Linear probing from the key's hash; the table is never more than half full, and the trip count is bounded by its size anyway.
+C4S_HD bool book_probe(const uint64_t* book, uint32_t log2_book, uint64_t key, int& score) {
+  const uint64_t last = (1ull << log2_book) - 1;
+  uint64_t i = tt_index(key, log2_book);
+  for (uint64_t trip = 0; trip <= last; ++trip) {
+    const uint64_t e = book[i];
+    if (e == 0) return false;
+    if ((e & kKeyMask) == key) { score = (int)(e >> 56) - kUpperBias; return true; }
+    i = (i + 1) & last;
+  }
+  return false;
+}
+
 // Row-major (bit = 7 row + col, c4_device.hpp) -> this layout.
 C4S_HD uint64_t from_row_major(uint64_t x) {
   uint64_t r = 0;
@@ -143,6 +169,20 @@ struct Lane {
   // not expand, nothing changed; save() and the stack's sp frames are the whole search.
   template <typename Word>
   C4S_HD StepResult step(Word* stk, int stride, uint64_t* tt, uint32_t log2_entries, int64_t& budget) {
+    return step_impl<false>(stk, stride, tt, log2_entries, budget, nullptr, 0, 0);
+  }
+
+  // The same with a book (book_probe): a node entered with at most book_stones stones -- the largest stone count the book holds --
+  // is looked up by its canonical key, and a hit is a leaf with the exact score.
+  template <typename Word>
+  C4S_HD StepResult step(Word* stk, int stride, uint64_t* tt, uint32_t log2_entries, int64_t& budget, const uint64_t* book, uint32_t log2_book,
+                         int book_stones) {
+    return step_impl<true>(stk, stride, tt, log2_entries, budget, book, log2_book, book_stones);
+  }
+
+  template <bool BOOK, typename Word>
+  C4S_HD StepResult step_impl(Word* stk, int stride, uint64_t* tt, uint32_t log2_entries, int64_t& budget, const uint64_t* book, uint32_t log2_book,
+                              int book_stones) {
     bool have_ret = !enter;
     uint32_t w0 = 0;
     if (enter) {
@@ -157,6 +197,10 @@ struct Lane {
         const int mn = -(40 - n) / 2, mx = (41 - n) / 2;   // the opponent cannot win next; the mover cannot win now
         if (a < mn) { a = mn; if (a >= b) { v = a; leaf = true; } }
         if (!leaf && b > mx) { b = mx; if (a >= b) { v = b; leaf = true; } }
+        if (BOOK && !leaf && n <= book_stones) {
+          int exact = 0;
+          if (book_probe(book, log2_book, canonical_key(pos, mask), exact)) { v = exact; leaf = true; }
+        }
         if (!leaf) {
           const uint64_t key = pos + mask;
           const uint64_t e = tt[tt_index(key, log2_entries)];       // one 8-byte load: an entry is whole or absent

@@ -1,15 +1,23 @@
 """Exact solver on the GPU: what the reference gets from Pascal Pons' `c4solver` binary, its opening book and a rocksdb cache
 (rust/src/solver.rs), here a HIP alpha-beta search (include/c4a0_hip.h "exact solver", c4a0_amd/csrc/c4_solver.hip) with no
-binary, no book and no database.
+binary and no database, and with a book only of what it has solved itself.
 
     solver = c4a0_amd.Solver()
     r = solver.solve(positions)              # SolveResult: scores int16[P, 7] as `c4solver -a` prints them, solved bool[P]
     solver.score_policies(positions, pol)    # float32[P]: Solution::score_policy (solver.rs:201-228), NaN where unsolved
     result.solver_score(solver)              # PlayGamesResult / SearchResult: the reference's PlayGamesResult.score_policies
 
-There is no opening book: positions with few stones may exhaust `max_nodes_per_position` and come back with solved = False and a
-row of UNSOLVED.  The table of the `Solver` lives across calls (the role of the reference's CachingSolver): asking again later,
-or with a larger budget, continues from what was learned.
+Positions with few stones may exhaust `max_nodes_per_position` and come back with solved = False and a row of UNSOLVED.  The
+table of the `Solver` lives across calls (the role of the reference's CachingSolver): asking again later, or with a larger
+budget, continues from what was learned.  Two options reach further down the stone counts:
+
+    solver = c4a0_amd.Solver(book_entries=1 << 22)     # keep every exact score of a position with <= book_max_stones stones
+    solver.solve(positions, split_stones=14)           # a task out of budget with < 14 stones is replaced by its children
+    solver.save_book(path); solver.load_book(path)     # the book as a .npy of uint64 entries
+
+Splitting gives a hard position the width of the GPU -- thousands of cheaper tasks a stone deeper instead of seven lanes -- and the
+book keeps what that cost: the search kernel reads it, tasks are answered from it without a launch, and it can be saved.  There is
+still no book of openings computed elsewhere: how far down this reaches is a matter of budget.
 """
 from __future__ import annotations
 
@@ -90,7 +98,8 @@ def score_rows(scores: np.ndarray, policies: np.ndarray) -> np.ndarray:
 class SolveResult:
     """scores int16[P, 7]: per column what `c4solver -a` prints (FULL_COLUMN for a full column; positive = the side to move
     wins, larger = sooner), a row of UNSOLVED where `solved` is False.  stats: nodes, probes, launches, tasks, unsolved_tasks of
-    the call, and unique_positions (what was left after removing duplicates and mirror images)."""
+    the call, split_tasks, combined_nodes, dropped_tasks, book_hits_host, book_inserts, book_full (include/c4a0_hip.h
+    c4_solver_stats_ex), and unique_positions (what was left after removing duplicates and mirror images)."""
 
     __slots__ = ("scores", "solved", "stats")
 
@@ -117,24 +126,30 @@ class SolveResult:
 
 class Solver:
     """An exact Connect Four solver on one GPU.  `tt_entries`: entries of its transposition table (a power of two, 8 bytes
-    each; the default 2^24 = 128 MB), kept until `close()`."""
+    each; the default 2^24 = 128 MB), kept until `close()`.  `book_entries`: 0, or the entries of a book of exact scores (a power
+    of two, 8 bytes each on the device and on the host) that keeps every position of at most `book_max_stones` stones the solver
+    obtains an exact score for; it is never more than half full and nothing leaves it."""
 
-    def __init__(self, device=None, tt_entries: int = 1 << 24):
+    def __init__(self, device=None, tt_entries: int = 1 << 24, book_entries: int = 0, book_max_stones: int = 20):
         import torch
 
         from ._lib import check, lib
 
         if int(tt_entries) < 16 or int(tt_entries) > 1 << 32 or int(tt_entries) & (int(tt_entries) - 1):
             raise ValueError("tt_entries must be a power of two between 16 and 2**32")
+        if int(book_entries) != 0 and (int(book_entries) < 16 or int(book_entries) > 1 << 28 or int(book_entries) & (int(book_entries) - 1)):
+            raise ValueError("book_entries must be 0 or a power of two between 16 and 2**28")
+        if not 1 <= int(book_max_stones) <= 41:
+            raise ValueError("book_max_stones must be between 1 and 41")
         if not torch.cuda.is_available():
             raise RuntimeError("c4a0_amd.Solver needs a HIP device: the solver is a GPU kernel and there is no CPU path")
         dev = torch.device("cuda" if device is None else device)
         if dev.type != "cuda":
             raise ValueError("Solver runs on a HIP device")
         self.device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-        self.tt_entries = int(tt_entries)
+        self.tt_entries, self.book_entries, self.book_max_stones = int(tt_entries), int(book_entries), int(book_max_stones)
         self._h = C.c_void_p()
-        check(lib().c4_solver_create(self.tt_entries, self.device.index, C.byref(self._h)))
+        check(lib().c4_solver_create_ex(self.tt_entries, self.book_entries, self.book_max_stones, self.device.index, C.byref(self._h)))
 
     def close(self) -> None:
         h, self._h = getattr(self, "_h", None), None
@@ -155,14 +170,63 @@ class Solver:
         except Exception:
             pass
 
-    def solve(self, positions, *, nodes_per_launch: Optional[int] = None, max_nodes_per_position: Optional[int] = None) -> SolveResult:
+    def _book_entries(self) -> np.ndarray:
+        from ._lib import check, lib
+
+        if not self._h:
+            raise RuntimeError("this Solver is closed")
+        n = C.c_uint64(0)
+        check(lib().c4_solver_book_export(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint64)
+        check(lib().c4_solver_book_export(self._h, out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value]
+
+    @property
+    def book_size(self) -> int:
+        """Entries in the book."""
+        from ._lib import check, lib
+
+        if not self._h:
+            raise RuntimeError("this Solver is closed")
+        n = C.c_uint64(0)
+        check(lib().c4_solver_book_export(self._h, None, 0, C.byref(n)))
+        return int(n.value)
+
+    def save_book(self, path) -> int:
+        """Write the book's entries to `path` as a .npy of uint64 (the name as given: no suffix is added); returns how many."""
+        entries = self._book_entries()
+        with open(path, "wb") as f:
+            np.save(f, entries)
+        return len(entries)
+
+    def load_book(self, path) -> int:
+        """Add the entries of a file written by `save_book` to the book; returns how many the file held.  Every entry is checked
+        (include/c4a0_hip.h c4_solver_book_import): a ValueError names the first bad one, and then nothing was added."""
+        from ._lib import ERR_BAD_ARG, check, lib
+
+        if not self._h:
+            raise RuntimeError("this Solver is closed")
+        entries = np.load(path, allow_pickle=False)
+        if entries.dtype != np.uint64 or entries.ndim != 1:
+            raise ValueError("a book file holds a one-dimensional uint64 array")
+        entries = np.ascontiguousarray(entries)
+        status = lib().c4_solver_book_import(self._h, entries.ctypes.data, len(entries))
+        if status == ERR_BAD_ARG:
+            raise ValueError(lib().c4_last_error_string().decode())
+        check(status)
+        return len(entries)
+
+    def solve(self, positions, *, nodes_per_launch: Optional[int] = None, max_nodes_per_position: Optional[int] = None,
+              split_stones: Optional[int] = None, split_max_tasks: Optional[int] = None) -> SolveResult:
         """Solve every position of `positions` -- a sequence of (mask, value) or a uint64[P, 2] array, as `search_positions`
         takes them; each must be non-terminal.  Duplicates are solved once and a position and its mirror image as one.
         `nodes_per_launch`: node visits a GPU lane gets per kernel launch; `max_nodes_per_position`: visits after which a
-        child's search is given up (None: the library's defaults, include/c4a0_hip.h)."""
+        child's search is given up (None: the library's defaults, include/c4a0_hip.h).  `split_stones`: a task given up with
+        fewer stones than this is replaced by its children instead (None or 0: never); `split_max_tasks`: tasks one call may make
+        that way (None: 2^18), a bound on device memory at 392 bytes per task."""
         import torch
 
-        from ._lib import SolverStats, check, lib
+        from ._lib import SolverOptions, SolverStatsEx, check, lib
         from .api import _positions_array
 
         if not self._h:
@@ -171,13 +235,17 @@ class Solver:
         for name, v in (("nodes_per_launch", nodes_per_launch), ("max_nodes_per_position", max_nodes_per_position)):
             if v is not None and not (1 <= int(v) < 1 << 40):
                 raise ValueError(f"{name} must be between 1 and 2**40")
+        if split_stones is not None and not (0 <= int(split_stones) <= 42):
+            raise ValueError("split_stones must be between 0 and 42")
+        if split_max_tasks is not None and not (1 <= int(split_max_tasks) <= 1 << 24):
+            raise ValueError("split_max_tasks must be between 1 and 2**24")
         term = is_terminal(pos[:, 0], pos[:, 1])
         if bool(term.any()):
             raise ValueError(f"position {int(np.flatnonzero(term)[0])}: the position is terminal (nothing to solve)")
         n = len(pos)
         if n == 0:
             return SolveResult(np.zeros((0, 7), dtype=np.int16), np.zeros(0, dtype=bool),
-                               dict(nodes=0, probes=0, launches=0, tasks=0, unsolved_tasks=0, unique_positions=0))
+                               dict(SolverStatsEx().as_dict(), unique_positions=0))
         # a position and its mirror image are one problem: the smaller (mask, value) of the two is solved, the row reversed on the way back
         mm, mv = _mirror(pos[:, 0]), _mirror(pos[:, 1])
         flipped = (mm < pos[:, 0]) | ((mm == pos[:, 0]) & (mv < pos[:, 1]))
@@ -186,10 +254,12 @@ class Solver:
         uniq = np.ascontiguousarray(uniq, dtype=np.uint64)
         scores = np.empty((len(uniq), 7), dtype=np.int16)
         solved = np.empty(len(uniq), dtype=np.uint8)
-        st = SolverStats()
+        st = SolverStatsEx()
+        opt = SolverOptions(C.sizeof(SolverOptions), int(nodes_per_launch or 0), int(max_nodes_per_position or 0), int(split_stones or 0),
+                            int(split_max_tasks or 0))
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        check(lib().c4_solver_solve(self._h, uniq.ctypes.data, len(uniq), int(nodes_per_launch or 0), int(max_nodes_per_position or 0),
-                                    scores.ctypes.data, solved.ctypes.data, C.byref(st), C.c_void_p(stream)))
+        check(lib().c4_solver_solve_ex(self._h, uniq.ctypes.data, len(uniq), C.byref(opt), scores.ctypes.data, solved.ctypes.data, C.byref(st),
+                                       C.c_void_p(stream)))
         inverse = np.asarray(inverse).reshape(-1)
         rows = scores[inverse]
         rows[flipped] = rows[flipped][:, ::-1]

@@ -800,7 +800,7 @@ int c4_head_out_f32(const float* hidden_policy_dev, const float* hidden_value_de
  * visits (a visit = a node whose moves are generated; children answered at once by the rules, the window or the table belong to
  * their parent's visit); a task unfinished then keeps its stack (320 bytes, in device memory for the length of the call) and goes on in
  * the next launch; a task that has used max_nodes_per_position visits is given up.  A position with a task given up is returned with
- * solved = 0 and seven C4_SOLVE_UNSOLVED.  There is no opening book, so positions with few stones end there: the limit of this solver, not an error. */
+ * solved = 0 and seven C4_SOLVE_UNSOLVED.  Positions with few stones end there unless tasks are split and a book is kept (below). */
 #define C4_SOLVE_FULL_COLUMN (-1000)
 #define C4_SOLVE_UNSOLVED (-32768)                    /* INT16_MIN */
 #define C4_SOLVER_TT_ENTRIES (1ull << 24)             /* the default table: 2^24 entries = 128 MB */
@@ -825,6 +825,58 @@ int c4_solver_destroy(c4_solver* handle);
  * One call at a time per handle (others wait). */
 int c4_solver_solve(c4_solver* handle, const uint64_t* positions_host, uint64_t n_positions, uint64_t nodes_per_launch,
                     uint64_t max_nodes_per_position, int16_t* scores_out, uint8_t* solved_out, c4_solver_stats* stats_out, void* stream);
+
+/* ---- exact solver: splitting and the book (added functions only: C4_ABI_VERSION stays what it was) ----------------------------
+ * Splitting.  One lane per task is all the width a hard position gets, and a task given up at max_nodes_per_position leaves nothing
+ * behind but bounds in a lossy table.  With split_stones > 0, a task that reaches max_nodes_per_position unsolved, has fewer than
+ * split_stones stones and comes while the call has made fewer than split_max_tasks tasks by splitting is REPLACED by its children: one
+ * task per non-losing move, a stone deeper and each far cheaper, with a fresh budget.  Equal and mirrored positions are one node of the
+ * scheduler's graph; a node whose children are all known has the value max(-child).  A task that can neither finish nor split fails
+ * with everything above it: the asked positions that depend on it come back solved = 0 with seven C4_SOLVE_UNSOLVED, as before, and
+ * tasks that only they needed are dropped.  The task array and the stack store on the device grow between launches (392 bytes per
+ * task in flight); split_max_tasks bounds them -- a memory bound, not a tuning result.
+ *
+ * The book.  A solver created with book_entries > 0 keeps every exact score it obtains for a position of at most book_max_stones
+ * stones -- a finished task, a combined node, an asked position whose seven scores are known -- in a lossless open-addressed table:
+ * one 64-bit word per entry, the canonical key (the smaller of the 49-bit key of the position and of its mirror image) | (score + 32)
+ * << 56, 0 = empty.  Only the host inserts, between launches, and sends the new words to the device's copy before the next launch; the kernel only
+ * reads: on entering a node with no more stones than the book's largest entry it probes, and a hit is a leaf with the exact score.
+ * A child found in the book when tasks are made needs no task (book_hits_host): asking again for a solved position costs no launch.
+ * Nothing is evicted; above half full nothing more is inserted (book_full counts what was turned away).  The book lives as long as
+ * the handle and can be exported and imported. */
+#define C4_SOLVER_SPLIT_MAX_TASKS (1ull << 18)        /* the default of split_max_tasks: ~100 MB of device memory at 392 bytes per task */
+#define C4_SOLVER_BOOK_MAX_STONES 20u                 /* the default of book_max_stones */
+typedef struct {
+  uint64_t struct_size;             /* sizeof(c4_solver_options) */
+  uint64_t nodes_per_launch;        /* 0 = C4_SOLVER_NODES_PER_LAUNCH */
+  uint64_t max_nodes_per_position;  /* 0 = C4_SOLVER_MAX_NODES_PER_POSITION */
+  uint64_t split_stones;            /* tasks with fewer stones may be split; 0 = never split (c4_solver_solve) */
+  uint64_t split_max_tasks;         /* tasks one call may create by splitting; 0 = C4_SOLVER_SPLIT_MAX_TASKS */
+} c4_solver_options;
+typedef struct {
+  uint64_t nodes, probes, launches, tasks, unsolved_tasks; /* as c4_solver_stats; tasks includes those made by splitting */
+  uint64_t split_tasks;     /* tasks made by splitting */
+  uint64_t combined_nodes;  /* split nodes whose value came from their children */
+  uint64_t dropped_tasks;   /* tasks taken off the live list because every asked position that needed them had failed */
+  uint64_t book_hits_host;  /* children answered from the book when tasks were made */
+  uint64_t book_inserts;    /* entries the call added to the book */
+  uint64_t book_full;       /* exact scores not kept because the book was half full */
+} c4_solver_stats_ex;
+
+/* c4_solver_create with a book of book_entries entries (0 = none; else a power of two, 16 .. 2^28; 8 bytes each on the device and on
+ * the host) that keeps positions of at most book_max_stones stones (0 = C4_SOLVER_BOOK_MAX_STONES; at most 41). */
+int c4_solver_create_ex(uint64_t tt_entries, uint64_t book_entries, uint32_t book_max_stones, int32_t device, c4_solver** out);
+/* c4_solver_solve with options (NULL = all defaults, which is c4_solver_solve(.., 0, 0, ..)) and the longer statistics (may be NULL). */
+int c4_solver_solve_ex(c4_solver* handle, const uint64_t* positions_host, uint64_t n_positions, const c4_solver_options* options,
+                       int16_t* scores_out, uint8_t* solved_out, c4_solver_stats_ex* stats_out, void* stream);
+/* The book's entries in table order: *n_out = how many there are, of which the first min(*n_out, cap) are written to out. */
+int c4_solver_book_export(c4_solver* handle, uint64_t* out, uint64_t cap, uint64_t* n_out);
+/* Add entries to the book: all of them or, with C4_ERR_BAD_ARG naming the index of the first bad one, none.  An entry is valid when its
+ * key decodes to a legal position (bits 49..55 clear; no stones in the sentinel row; stone counts that fit the side
+ * to move; no four on the board), is the canonical key of its mirror pair, has at most book_max_stones stones n, and its score lies in
+ * [-(42 - n) / 2, (43 - n) / 2], and the book or an earlier entry does not hold the same position with another score (with the same
+ * score it is a duplicate and adds nothing).  Entries that would fill the book beyond half are refused as a whole too. */
+int c4_solver_book_import(c4_solver* handle, const uint64_t* entries, uint64_t n);
 
 #ifdef __cplusplus
 }
