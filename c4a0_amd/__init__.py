@@ -1,7 +1,8 @@
 """c4a0_amd -- MI355X-native self-play generator for c4a0 (Connect Four AlphaZero).
 
-Hot path only: the GPU-resident batched MCTS behind the reference's `c4a0_rust.play_games`
-API (reference rust/src/pybridge.rs:20-53).  See DESIGN.md.
+The GPU-resident batched MCTS behind the reference's `c4a0_rust.play_games` API (reference
+rust/src/pybridge.rs:20-53) and the generation step that trains the next network from its games
+(`train_single_gen`, reference src/c4a0/training.py).  See DESIGN.md.
 """
 N_COLS = 7           # reference rust/src/lib.rs:28
 N_ROWS = 6           # reference rust/src/lib.rs:29
@@ -20,6 +21,9 @@ def __getattr__(name):  # torch / the HIP library are loaded on first use of the
     if name in ("Solver", "SolveResult", "SolverScore"):   # exact solver on the GPU: solve / score_policies, and solver_score of results
         from . import solver
         return getattr(solver, name)
+    if name in ("train_single_gen", "training_loop", "TrainingGen", "TrainConfig"):   # a generation: self-play, then the next network
+        from . import training
+        return getattr(training, name)
     if name == "SearchResult":
         from .results import SearchResult
         return SearchResult

@@ -783,6 +783,33 @@ int c4_head_out_f32(const float* hidden_policy_dev, const float* hidden_value_de
                     const float* b_policy_dev, const float* b_value_dev, uint32_t n_boards, uint32_t policy_features, uint32_t value_features,
                     uint32_t policy_row_stride, uint32_t value_row_stride, float* logprobs, float* q, float* preact, void* stream);
 
+/* ---- training the heads' hidden blocks (added functions only: C4_ABI_VERSION stays what it was) ------------------------------------
+ * One hidden block of a head is Linear(k, n) -> BatchNorm1d(n) in train mode -> ReLU (nn.py:75-100).  Its forward product z = x W^T + b
+ * is c4_linear_f32(relu = 0); the calls below are the rest of a training step.  All f32, row-major, on `stream`; n % 32 == 0,
+ * k % 16 == 0, leading dimensions multiples of 4 and at least the row length, arrays 16-byte aligned (else C4_ERR_BAD_ARG, nothing is
+ * launched).  Every output is a fixed function of the inputs: each sum has one order that the shape alone decides, no atomics -- two
+ * calls give the same bytes.  No [m][.] matrix is copied or transposed: activations and gradients are read where they lie. */
+
+/* mean[c], var[c]: the batch mean and the BIASED batch variance (sum (z - mean)^2 / m, two passes) of column c of z [m][ldz];
+ * y[r][c] = relu(((z[r][c] - mean[c]) * rstd[c]) * gamma[c] + beta[c]), rstd = 1 / sqrt(var + eps), y [m][ldy].  m >= 2. */
+int c4_train_bn_relu_fwd_f32(const float* z_dev, const float* gamma_dev, const float* beta_dev, float eps, uint32_t m, uint32_t n, uint32_t ldz,
+                             uint32_t ldy, float* y_dev, float* mean_dev, float* var_dev, void* stream);
+/* The backward of the call above from dy [m][lddy], the z, mean and var it was given / wrote: with g = dy where the pre-activation,
+ * recomputed by the forward's own operations, is > 0, else 0 (ReLU'(0) = 0), and xh = ((z - mean) - corr) * rstd, corr = the
+ * mean of the deviations z - mean (what the f32 mean is off by: without it sum_r dz, 0 in real numbers, is rounding noise times rstd^2):
+ *   dbeta = sum_r g,  dgamma = sum_r g xh,  dz = gamma rstd ((g - dbeta / m) - xh dgamma / m), dz [m][lddz].  m >= 2. */
+int c4_train_bn_relu_bwd_f32(const float* dy_dev, const float* z_dev, const float* mean_dev, const float* var_dev, const float* gamma_dev,
+                             const float* beta_dev, float eps, uint32_t m, uint32_t n, uint32_t lddy, uint32_t ldz, uint32_t lddz, float* dz_dev,
+                             float* dgamma_dev, float* dbeta_dev, void* stream);
+/* dx[r][c] = sum_j dz[r][j] w[j][c]: dz [m][ldz] (n columns), w [n][k], dx [m][ldx] (k columns).  One f32-MFMA chain per element over
+ * j in the order of c4_linear_f32's k.  Any m (m == 0: nothing to do). */
+int c4_train_linear_dgrad_f32(const float* dz_dev, const float* w_dev, float* dx_dev, uint32_t m, uint32_t n, uint32_t k, uint32_t ldz,
+                              uint32_t ldx, void* stream);
+/* dw[j][c] = sum_r dz[r][j] x[r][c] and db[j] = sum_r dz[r][j]: dz [m][ldz] (n columns), x [m][ldx] (k columns), dw [n][k] (dense),
+ * db [n].  One f32-MFMA chain per element of dw over the batch rows; rows past m contribute nothing.  m >= 1. */
+int c4_train_linear_wgrad_f32(const float* dz_dev, const float* x_dev, float* dw_dev, float* db_dev, uint32_t m, uint32_t n, uint32_t k,
+                              uint32_t ldz, uint32_t ldx, void* stream);
+
 /* ---- exact solver ----------------------------------------------------------------------------------------------------------
  * What the reference gets from Pascal Pons' c4solver binary, its opening book and a rocksdb cache (rust/src/solver.rs): here a HIP
  * alpha-beta search with no binary, no book and no database.  These calls only ADD functions: C4_ABI_VERSION stays what it was.

@@ -1,0 +1,149 @@
+"""The training kernels of the heads' hidden blocks beside the stock PyTorch ops, on the GPU -> profiles/train_rate.json.
+
+    python tools/train_rate.py [out.json] [--no-generation] [--max-epochs E]
+
+(a) At m = 2 000 rows, F = 1 344 (the default network's heads at the reference's training batch): every kernel of c4_train.hip and
+    the forward c4_linear_f32 beside the PyTorch op that does the same job on the same tensors -- F.linear, dz @ W, dz.T @ x (+ the
+    column sum for db), F.batch_norm(training=True) + ReLU forward and their autograd backward.  Device events round 20 launches,
+    warmed up, the two sides ALTERNATING, medians of 7 pairs with their spreads.
+(b) The whole optimiser step (forward_train, loss, backward, Adam) of the default network ModelConfig(1, 32, 4, 2) at batch 2 000 with
+    heads="hip" against heads="torch", same timing scheme round 5 steps.  `c4a0_amd.train_heads.AUTO_HEADS` (what heads="auto" means)
+    is the faster of the two in the recorded file.
+(c) One default-shaped generation through train_single_gen (1 700 games, n = 1 400, batch 2 000; --max-epochs, default 10, instead
+    of the reference's 100 so that the run stays short: train_s scales with the epochs run): wall seconds of play / split / train.
+Speed is recorded here, never asserted in a test."""
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import tempfile
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from c4a0_amd import _lib  # noqa: E402
+
+dev = torch.device("cuda:0")
+p = lambda t: C.c_void_p(t.data_ptr())
+stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+M, FEAT, EPS = 2000, 1344, 1e-5
+
+
+def time_us(fn, launches=20):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(launches):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / launches * 1e3
+
+
+def ab(fa, fb, pairs=7, launches=20):
+    """medians (us per call) of `pairs` alternating timings of two callables, and their spreads"""
+    for _ in range(3):
+        fa()
+        fb()
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(pairs):
+        ta.append(time_us(fa, launches))
+        tb.append(time_us(fb, launches))
+    return {"hip_us": statistics.median(ta), "torch_us": statistics.median(tb), "hip_range_us": [min(ta), max(ta)], "torch_range_us": [min(tb), max(tb)]}
+
+
+def kernels():
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(0)
+    m, n, k = M, FEAT, FEAT
+    x, dz, dy = (torch.randn(m, FEAT, generator=g).to(dev) for _ in range(3))
+    w = (torch.randn(n, k, generator=g) / k ** 0.5).to(dev)
+    b, gamma, beta = torch.randn(n, generator=g).to(dev), (torch.rand(n, generator=g) + 0.5).to(dev), torch.randn(n, generator=g).to(dev)
+    z, y, dx, dzo = (torch.empty((m, n), device=dev) for _ in range(4))
+    dw = torch.empty((n, k), device=dev)
+    mean, var, db, dgamma, dbeta = (torch.empty(n, device=dev) for _ in range(5))
+    ck = _lib.check
+    out = {}
+    flop = 2.0 * m * n * k
+    out["linear_fwd"] = ab(lambda: ck(L.c4_linear_f32(p(x), p(w), p(b), p(z), m, n, k, k, n, 0, stream())), lambda: F.linear(x, w, b))
+    out["dgrad"] = ab(lambda: ck(L.c4_train_linear_dgrad_f32(p(dz), p(w), p(dx), m, n, k, n, k, stream())), lambda: dz @ w)
+    out["wgrad"] = ab(lambda: ck(L.c4_train_linear_wgrad_f32(p(dz), p(x), p(dw), p(db), m, n, k, n, k, stream())), lambda: (dz.t() @ x, dz.sum(0)))
+    for name in ("linear_fwd", "dgrad", "wgrad"):
+        out[name]["hip_tflops"] = flop / out[name]["hip_us"] * 1e-6
+        out[name]["torch_tflops"] = flop / out[name]["torch_us"] * 1e-6
+    ck(L.c4_linear_f32(p(x), p(w), p(b), p(z), m, n, k, k, n, 0, stream()))
+    out["bn_relu_fwd"] = ab(lambda: ck(L.c4_train_bn_relu_fwd_f32(p(z), p(gamma), p(beta), EPS, m, n, n, n, p(y), p(mean), p(var), stream())),
+                            lambda: torch.relu(F.batch_norm(z, None, None, gamma, beta, True, 0.1, EPS)))
+    zt, gt, bt = z.clone().requires_grad_(), gamma.clone().requires_grad_(), beta.clone().requires_grad_()
+    yt = torch.relu(F.batch_norm(zt, None, None, gt, bt, True, 0.1, EPS))
+    out["bn_relu_bwd"] = ab(lambda: ck(L.c4_train_bn_relu_bwd_f32(p(dy), p(z), p(mean), p(var), p(gamma), p(beta), EPS, m, n, n, n, n, p(dzo), p(dgamma),
+                                                                 p(dbeta), stream())),
+                            lambda: torch.autograd.grad(yt, (zt, gt, bt), dy, retain_graph=True))
+    return out
+
+
+def whole_step():
+    from c4a0_amd import training as T
+    from c4a0_amd.nn import ConnectFourNet, ModelConfig
+    from c4a0_amd.train_heads import forward_train
+
+    torch.manual_seed(0)
+    g = torch.Generator().manual_seed(1)
+    cell = torch.randint(0, 3, (M, 6, 7), generator=g)
+    batch = (torch.stack([cell == 1, cell == 2], 1).float().to(dev), torch.softmax(torch.randn(M, 7, generator=g), 1).to(dev),
+             (torch.rand(M, generator=g) * 2 - 1).to(dev), (torch.rand(M, generator=g) * 2 - 1).to(dev))
+    steps = {}
+    for heads in ("hip", "torch"):
+        model = ConnectFourNet(ModelConfig(1, 32, 4, 2)).to(dev).train()
+        opt = torch.optim.Adam(model.parameters(), lr=2e-3, weight_decay=4e-4)
+
+        def step(model=model, opt=opt, heads=heads):
+            opt.zero_grad(set_to_none=True)
+            T.loss(forward_train(model, batch[0], heads), batch)[0].backward()
+            opt.step()
+
+        steps[heads] = step
+    r = ab(steps["hip"], steps["torch"], launches=5)
+    return {"batch": M, "model": [1, 32, 4, 2], "hip_ms": r["hip_us"] * 1e-3, "torch_ms": r["torch_us"] * 1e-3,
+            "hip_range_ms": [v * 1e-3 for v in r["hip_range_us"]], "torch_range_ms": [v * 1e-3 for v in r["torch_range_us"]]}
+
+
+def generation(max_epochs: int, heads: str):
+    from c4a0_amd import training as T
+    from c4a0_amd.nn import ModelConfig
+
+    with tempfile.TemporaryDirectory() as base:
+        torch.manual_seed(0)
+        parent = T.TrainingGen.load_latest_with_default(base, 1400, 6.6, 0.01, 2000, 2000, ModelConfig(1, 32, 4, 2), T.TrainConfig({0: 2e-3}, 4e-4))
+        timings = {}
+        gen = T.train_single_gen(base, dev, parent, 1700, 1400, 6.6, 0.01, 2000, 2000, heads=heads, max_epochs=max_epochs, timings=timings)
+        timings.update(heads=heads, max_epochs=max_epochs, val_loss=gen.val_loss, games=1700, n_mcts_iterations=1400, batch=2000)
+        return timings
+
+
+def main():
+    import argparse
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "train_rate.json"))
+    ap.add_argument("--no-generation", action="store_true")
+    ap.add_argument("--max-epochs", type=int, default=10)
+    a = ap.parse_args()
+    out_path, max_epochs = a.out, a.max_epochs
+    res = {"device": torch.cuda.get_device_name(0), "shape": {"m": M, "n": FEAT, "k": FEAT}, "kernels": kernels(), "step": whole_step()}
+    print(json.dumps(res, indent=1), flush=True)
+    if not a.no_generation:
+        faster = "hip" if res["step"]["hip_ms"] < res["step"]["torch_ms"] else "torch"
+        res["generation"] = generation(max_epochs, faster)
+        print(json.dumps(res["generation"], indent=1), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
