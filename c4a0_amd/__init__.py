@@ -24,6 +24,12 @@ def __getattr__(name):  # torch / the HIP library are loaded on first use of the
     if name in ("train_single_gen", "training_loop", "TrainingGen", "TrainConfig"):   # a generation: self-play, then the next network
         from . import training
         return getattr(training, name)
+    if name in ("play_tournament", "TournamentResult", "Player", "ModelPlayer", "RandomPlayer", "UniformPlayer", "gen_players"):   # ranking networks
+        from . import tournament
+        return getattr(tournament, name)
+    if name == "BuiltinEvaluator":   # the anchors as device evaluators (also single evaluators of play_games / search_positions / Engine)
+        from .builtin import BuiltinEvaluator
+        return BuiltinEvaluator
     if name == "SearchResult":
         from .results import SearchResult
         return SearchResult

@@ -31,6 +31,7 @@ HOLD_POLL_UNKNOWN = 0xFFFFFFFF
 MAX_SAMPLES_PER_GAME = 43
 ROUTE_MAX_MODELS = 32     # include/c4a0_hip.h C4_ROUTE_MAX_MODELS: models one routed batch (c4_session_route_leaves) may hold
 GROUPED_ROW_ALIGN = 128   # include/c4a0_hip.h C4_GROUPED_ROW_ALIGN == c4_grouped_row_align(): segments of a grouped batch are multiples of it
+BUILTIN_UNIFORM, BUILTIN_RANDOM = 0, 1   # include/c4a0_hip.h C4_BUILTIN_*: the kinds of c4_builtin_eval (c4a0_amd/builtin.py)
 ABI_VERSION = 14   # include/c4a0_hip.h C4_ABI_VERSION: the signatures below are that version's
 STRUCT_LAYOUT_SINCE = 7   # the ABI version that last changed a structure's layout (c4_config.reclaim_period, c4_counters.reclaim_*)
 
@@ -182,6 +183,9 @@ SIGNATURES = {
     "c4_conv_tower_bf16_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "c4_linear_bf16_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "c4_head_out_bf16_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "c4_builtin_eval": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    "c4_builtin_eval_grouped": (C.c_int, [_vp, _vp, C.c_uint32, _P(C.c_uint32), _P(C.c_uint64), _P(C.c_uint64), C.c_uint32, _vp, _vp]),
+    "c4_builtin_eval_host": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "c4_dirichlet": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint64, _vp, _vp]),
     "c4_sample_move": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "c4_conv_tower_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),

@@ -186,7 +186,8 @@ class _GroupedModelEvaluator:
     """Device-mode tournaments from a HIP graph: what _MultiModelEvaluator does with a sort, two host reads and one eager chain per
     model is here pure device work of a fixed shape.  c4_session_route_leaves groups the resident games' leaves by the model that
     must answer them (segment bounds in device memory only), the grouped bf16 chain (c4a0_amd.nn.GroupedNets) evaluates every
-    segment with its model's weights in one launch per layer, and every slot takes its answer from its row.  A row's outputs are
+    segment with its model's weights in one launch per layer (built-in players' segments: one launch of c4_builtin_eval_grouped,
+    c4a0_amd.builtin.GroupedPlayers), and every slot takes its answer from its row.  A row's outputs are
     the bits its model's InferenceNet computes for that position, so the records are those of the eager path.
 
     __call__ is the evaluate() form (warm-up of capture_steps, observers): the answers go to the bound logprobs / q tensors
@@ -283,7 +284,9 @@ def play_games(reqs: Sequence[GameMetadata], max_nn_batch_size: int, n_mcts_iter
 
     Tournaments (evaluator={model_id: evaluator, ...}): unmodified bf16 `InferenceNet`s of one architecture are stacked
     (`c4a0_amd.nn.GroupedNets`) and the job is replayed from a HIP graph -- the leaves routed by model on the device, one grouped launch
-    per layer, no host synchronisation per round; anything else is evaluated per model with a gathered batch each round.
+    per layer, no host synchronisation per round; built-in players (`c4a0_amd.builtin.BuiltinEvaluator`: the anchors `random` and
+    `uniform` of `c4a0_amd.tournament`) ride along with one launch for all their segments, with or without networks; anything else
+    is evaluated per model with a gathered batch each round.
     stats["multi_model"] is "grouped" or "eager", stats["multi_model_reason"] why not grouped.  Same records either way."""
     reqs = list(reqs)
     if py_eval_pos_cb is not None and evaluator is None and getattr(py_eval_pos_cb, "device_evaluator", None) is not None:
@@ -399,7 +402,8 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
         if host_loop == "native":
             raise TypeError(f"host_loop='native': {why}")
     multi = evaluator is not None and isinstance(evaluator, dict)
-    # Tournaments: bf16 networks of one architecture on the hand-written kernels are stacked (nn.GroupedNets) and the job is replayed
+    # Tournaments: bf16 networks of one architecture on the hand-written kernels are stacked (nn.GroupedNets), built-in players
+    # (builtin.BuiltinEvaluator) answer their segments with one more launch (builtin.GroupedPlayers), and the job is replayed
     # from a HIP graph on one session (_GroupedModelEvaluator); anything else keeps the eager per-model path (_MultiModelEvaluator)
     grouped, grouped_why = None, None
     if multi:
@@ -413,7 +417,8 @@ def _play_locked(reqs, max_nn_batch_size, n_mcts_iterations, c_exploration, c_pl
                 not (torch.device(device).index is None and torch.device(device).type == "cuda"):
             grouped_why = "device= names another device than the evaluators'"
         if grouped_why is None:
-            grouped = GroupedNets(evaluator)
+            from .builtin import GroupedPlayers
+            grouped = GroupedPlayers(evaluator)   # (networks only: GroupedNets' chain, launch for launch)
             device, planes_dtype = grouped.device, torch.bfloat16
     if planes_dtype is None:   # hand a bf16 network bf16 planes (0/1 are exact): no conversion kernel per step
         planes_dtype = torch.bfloat16 if getattr(evaluator, "dtype", None) == torch.bfloat16 else torch.float32

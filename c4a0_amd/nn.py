@@ -846,12 +846,17 @@ class GroupedNets:
 
     @staticmethod
     def refusal(nets: dict) -> Optional[str]:
-        """None, or the reason these evaluators cannot be grouped (then a tournament takes the eager path).  Needs no GPU."""
+        """None, or the reason these evaluators cannot be grouped (then a tournament takes the eager path).  Needs no GPU.
+        Accepted: unmodified bf16 InferenceNets of one architecture and / or built-in players (c4a0_amd.builtin.BuiltinEvaluator)."""
         from ._lib import ROUTE_MAX_MODELS
+        from .builtin import BuiltinEvaluator
 
-        evs = list(nets.values())
-        if not evs:
+        players = list(nets.values())
+        if not players:
             return "no evaluators"
+        # built-in players (c4a0_amd.builtin.BuiltinEvaluator) need no weights: c4_builtin_eval_grouped answers their segments of
+        # the routed batch beside the networks' chain (builtin.GroupedPlayers); the conditions below are the networks'
+        evs = [ev for ev in players if not isinstance(ev, BuiltinEvaluator)]
         for ev in evs:
             if not isinstance(ev, InferenceNet):
                 return "an evaluator is not a c4a0_amd.nn.InferenceNet"
@@ -859,8 +864,15 @@ class GroupedNets:
                 return "an evaluator overrides InferenceNet.forward (it must see every evaluation)"
             if getattr(ev, "head_dtype", None) is not None:
                 return "fp8 hidden layers run through the Python host loop (the grouped chain is bf16)"
-        if len(evs) > ROUTE_MAX_MODELS:
+        if len(players) > ROUTE_MAX_MODELS:
             return f"more than {ROUTE_MAX_MODELS} models"
+        builtins = [ev for ev in players if isinstance(ev, BuiltinEvaluator)]
+        home = (evs or builtins)[0].device
+        for ev in builtins:
+            if ev.device != home:
+                return f"the evaluators are on different devices ({home}, {ev.device})"
+        if not evs:   # built-in players alone: no chain, nothing more to ask
+            return None
         a = evs[0]
         for ev in evs:
             if len(ev.pol_w) < 2 or len(ev.val_w) < 2 or ev.merged_w1 is None:
@@ -886,6 +898,8 @@ class GroupedNets:
         why = GroupedNets.refusal(nets)
         if why is not None:
             raise ValueError(f"GroupedNets: {why}")
+        if not all(isinstance(ev, InferenceNet) for ev in nets.values()):
+            raise ValueError("GroupedNets stacks networks; built-in players go through c4a0_amd.builtin.GroupedPlayers")
         self.ids = [int(k) & ((1 << 64) - 1) for k in nets]
         evs = list(nets.values())
         a = evs[0]

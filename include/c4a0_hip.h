@@ -736,6 +736,46 @@ int c4_head_out_bf16_grouped(const void* hidden_policy_dev, const void* hidden_v
                              const float* b_policy_dev, const float* b_value_dev, const uint32_t* seg_start_dev, uint32_t n_models, uint32_t rows_cap,
                              uint32_t features, uint32_t policy_row_stride, uint32_t value_row_stride, float* answers_dev, void* stream);
 
+/* ---- built-in players (additive, ABI 14): the tournament's two weightless evaluators (src/c4a0/tournament.py:54-77), as PURE
+ * functions of (kind, seed, model id, position) -- an answer never depends on the batch, and a game can be replayed from outside.
+ * (The reference's RandomPlayer draws from torch's global generator: another answer at every call.  Here the draw is keyed by
+ * the position.)  One definition for the device kernels and the host twin: c4a0_amd/csrc/c4_builtin.hpp.
+ *
+ * The position is read from a row's two planes in their own order, cell i = 7 * row + col:
+ *     value = sum over i of [plane0[i] != 0] << i          mask = value | sum over i of [plane1[i] != 0] << i
+ * C4_BUILTIN_UNIFORM (tournament.py:67-77): seven logits of exactly 1.0f, q_penalty = q_no_penalty = 0.0f.
+ * C4_BUILTIN_RANDOM (tournament.py:54-64: logits in [0, 1), one q in [-1, 1) for both values), all arithmetic modulo 2^64:
+ *     G = 0x9E3779B97F4A7C15
+ *     mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  return z ^ z >> 31
+ *     k = mix(seed + G);  k = mix(k ^ model_id);  k = mix(k ^ mask);  k = mix(k ^ value)
+ *     u[j] = mix(k + (j + 1) * G) >> 40                   j = 0..7   (24 bits)
+ *     logit[j] = (float)u[j] * 2^-24                      j = 0..6
+ *     q = (float)((int)u[7] - 2^23) * 2^-23               q_penalty = q_no_penalty = q
+ * Every output is a dyadic rational that f32 holds exactly: no transcendental, no rounding; host and device agree bit for bit.
+ * The logits are raw (the tree's masked softmax normalises them, as for every evaluator). */
+#define C4_BUILTIN_UNIFORM 0
+#define C4_BUILTIN_RANDOM 1
+/* A plain batch, one lane per row: planes_dev [rows][2][6][7] in f32 (planes_dtype 0) or bf16 (1: the session's encoding), rows
+ * 8-byte aligned (read as 8-byte words) -> logits_out_dev f32 [rows][7], q_out_dev f32 [rows][2] (q_penalty, q_no_penalty).
+ * Nothing past `rows` is read or written.  rows == 0: C4_OK without a launch.  C4_ERR_BAD_ARG: another kind or dtype, a null or
+ * misaligned pointer.  No synchronisation; may be captured. */
+int c4_builtin_eval(const void* planes_dev, uint32_t planes_dtype, uint32_t rows, uint32_t kind, uint64_t seed, uint64_t model_id,
+                    float* logits_out_dev, float* q_out_dev, void* stream);
+/* The built-in players' segments of a grouped batch (the section above): planes_dev bf16 [rows_cap][2][6][7], segment m owns rows
+ * seg_start_dev[m] .. seg_start_dev[m + 1] - 1 (n_segments + 1 bounds in DEVICE memory, multiples of c4_grouped_row_align(); a
+ * tournament passes the router's array moved past the networks' segments) and is answered as player (kinds[m], seeds[m],
+ * model_ids[m]) into answers_dev f32 [rows_cap][9]: 7 logits, q_penalty, q_no_penalty -- c4_head_out_bf16_grouped's rows.  kinds,
+ * seeds and model_ids are HOST arrays of n_segments entries, read during the call and handed to the kernel BY VALUE in its
+ * arguments (at most C4_ROUTE_MAX_MODELS): a captured launch owns them, no device memory is involved.  Rows outside the given
+ * segments are not written; empty segments are legal; pad rows of a segment are computed like any row.  rows_cap a multiple of
+ * c4_grouped_row_align(); n_segments == 0 or rows_cap == 0: C4_OK without a launch.  No synchronisation; may be captured. */
+int c4_builtin_eval_grouped(const void* planes_dev, const uint32_t* seg_start_dev, uint32_t n_segments, const uint32_t* kinds,
+                            const uint64_t* seeds, const uint64_t* model_ids, uint32_t rows_cap, float* answers_dev, void* stream);
+/* The same code on the CPU (no device needed): planes f32 [rows][2][6][7] in host memory -> logits [rows][7], q_penalty [rows],
+ * q_no_penalty [rows] -- the three arrays of the reference's forward_numpy. */
+int c4_builtin_eval_host(const float* planes, uint64_t rows, uint32_t kind, uint64_t seed, uint64_t model_id, float* logits, float* q_penalty,
+                         float* q_no_penalty);
+
 /* ---- f32 evaluator (ABI 11): ConnectFourNet in f32 (the reference trains and evaluates in f32, nn.py:119-130) on gfx950's exact-f32
  * MFMA (v_mfma_f32_16x16x4_f32), for any width C = 1..64 (padded to Cp = 16 ceil(C / 16)), any number of residual blocks and any head
  * depth.  No bf16 anywhere: f32 planes, weights, activations, accumulation.  c4a0_amd/nn.py::pack_f32_weights packs the weights.
