@@ -17,6 +17,11 @@
 //     j), the weights one float per step from w[nb + 4 h + j][k0 + r].  D is dx[m0 + r][k0 + 4 h + e].
 // The batch-norm kernels give one workgroup 32 columns: 16 row groups x 32 columns of threads, per-thread sums over rows
 // rg, rg + 16, .., then the 16 partial sums added in order by the column's first thread.
+// Non-finite input: ReLU's predicate, in the forward and in the backward's mask, is PyTorch's !(pre <= 0), not pre > 0.  0 and -0 give 0
+// and ReLU'(0) = 0 as before, and for finite pre no bit differs; a NaN pre-activation passes: y is NaN and dy goes through the mask.
+// A column of z that holds a NaN or an infinity, or whose sum overflows, has a non-finite mean and variance, so all its
+// pre-activations are NaN: y, dz and dgamma of that column are NaN, dbeta is the column sum of dy, and no other column is touched
+// (F.batch_norm(training=True) + relu and their autograd do the same).  A poisoned batch shows in the loss; it is not trained on as zeros.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -61,7 +66,7 @@ __global__ __launch_bounds__(kBnCols * kBnGroups) void train_bn_relu_fwd(const f
   const float rstd = 1.0f / sqrtf(var + eps), g = gamma[col], b = beta[col];
   for (uint32_t row = rg; row < m; row += kBnGroups) {
     const float pre = (zc[(size_t)row * ldz] - mean) * rstd * g + b;
-    y[(size_t)row * ldy + col] = pre > 0.f ? pre : 0.f;
+    y[(size_t)row * ldy + col] = !(pre <= 0.f) ? pre : 0.f;   // a NaN passes
   }
   if (rg == 0) {
     mean_out[col] = mean;
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(kBnCols * kBnGroups) void train_bn_relu_bwd(const f
   for (uint32_t row = rg; row < m; row += kBnGroups) {
     const float d = z[(size_t)row * ldz + col] - mean;
     const float pre = d * rstd * g + b;                               // the forward's operations in the forward's order
-    const float gr = pre > 0.f ? dy[(size_t)row * lddy + col] : 0.f;  // ReLU'(0) = 0
+    const float gr = !(pre <= 0.f) ? dy[(size_t)row * lddy + col] : 0.f;   // ReLU'(0) = 0; the forward's predicate
     sb += gr;
     sg += gr * ((d - corr) * rstd);
   }
@@ -99,7 +104,7 @@ __global__ __launch_bounds__(kBnCols * kBnGroups) void train_bn_relu_bwd(const f
   for (uint32_t row = rg; row < m; row += kBnGroups) {
     const float d = z[(size_t)row * ldz + col] - mean;
     const float pre = d * rstd * g + b;
-    const float gr = pre > 0.f ? dy[(size_t)row * lddy + col] : 0.f;
+    const float gr = !(pre <= 0.f) ? dy[(size_t)row * lddy + col] : 0.f;
     dz[(size_t)row * lddz + col] = scale * ((gr - c1) - ((d - corr) * rstd) * c2);
   }
   if (rg == 0) {

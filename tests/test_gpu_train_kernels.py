@@ -27,7 +27,9 @@ BAD_ARG = 1
 SENT = 0x5A5A5A5A            # an f32 bit pattern (about 1.5e16) no kernel computes here
 U = 2.0 ** -24
 EPS = 1e-5
-NK = [(32, 32), (32, 672), (672, 32), (672, 672)]
+# k = 16 and 48, odd multiples of 16, take the 16-wide kernels train_dgrad<1, 2> and train_wgrad<2, 1>: (64, 48) at m = 64 is 2 x 3 dgrad
+# tiles in two workgroups, the second with idle wavefronts, (32, 16) at m = 1 a single live wavefront
+NK = [(32, 32), (32, 672), (672, 32), (672, 672), (32, 16), (64, 48), (672, 48)]
 M_GEMM = [1, 2, 3, 17, 64, 130, 257]      # 16-row tile tails and batch-reduction tails that are no multiple of 4
 M_BN = M_GEMM[1:]
 
