@@ -7,7 +7,7 @@
 #include "../c4a0_amd/csrc/c4_solver_core.hpp"
 
 extern "C" int emu_solve(const uint64_t* positions, uint64_t n_positions, uint64_t nodes_per_launch, uint64_t max_nodes, uint32_t log2_entries,
-                         int16_t* scores, uint8_t* solved, uint64_t* stats /* nodes, probes, launches, tasks, unsolved */) {
+                         int16_t* scores, uint8_t* solved, uint64_t* stats /* nodes, probes, launches, tasks, unsolved, the most nodes of one task */) {
   static std::vector<uint64_t> tt;
   tt.assign(1ull << log2_entries, 0);
   std::vector<c4s::Task> live, next;
@@ -34,7 +34,7 @@ extern "C" int emu_solve(const uint64_t* positions, uint64_t n_positions, uint64
       live.push_back(t);
     }
   }
-  for (int i = 0; i < 5; ++i) stats[i] = 0;
+  for (int i = 0; i < 6; ++i) stats[i] = 0;
   stats[3] = live.size();
   std::vector<uint32_t> store(live.size() * c4s::kStackWords);     // one stack per task: an unfinished search waits here
   while (!live.empty()) {
@@ -50,6 +50,7 @@ extern "C" int emu_solve(const uint64_t* positions, uint64_t n_positions, uint64
       while ((r = lane.step(stk, 1, tt.data(), log2_entries, budget)) == c4s::kRunning)
         if (lane.sp > c4s::kMaxDepth - 1 || ++trips > 64 * (nodes_per_launch + 64)) return 1;   // the bounds the kernel relies on
       t.nodes += lane.nodes; t.probes += lane.probes;
+      if (t.nodes > stats[5]) stats[5] = t.nodes;
       t.lo = (int8_t)lane.lo; t.hi = (int8_t)lane.hi;
       if (r == c4s::kSolved) { t.value = (int8_t)lane.lo; t.status = 1; }
       else lane.save(t);

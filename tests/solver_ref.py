@@ -1,4 +1,5 @@
-"""The plain C solver (tests/solver_ref.c, built here with gcc) behind numpy, the positions the solver tests share, and
+"""The plain C solver and its variant with a table (tests/solver_ref.c, built here with gcc) behind numpy, the positions the solver
+tests share, the recorded rows of 10 to 19 stones (tests/golden/solver_rows.npz), and
 Solution::score_policy (reference rust/src/solver.rs:201-228) restated one row at a time."""
 import ctypes as C
 import functools
@@ -24,6 +25,7 @@ def ref_lib() -> C.CDLL:
     L = C.CDLL(out)
     L.solve_scores.restype, L.solve_scores.argtypes = C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]
     L.brute_scores.restype, L.brute_scores.argtypes = None, [C.c_void_p, C.c_uint64, C.c_void_p]
+    L.solve_scores_tt.restype, L.solve_scores_tt.argtypes = C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]
     return L
 
 
@@ -36,6 +38,17 @@ def solve(positions):
     pos = _as_positions(positions)
     out = np.zeros((len(pos), 7), dtype=np.int16)
     nodes = ref_lib().solve_scores(pos.ctypes.data, len(pos), out.ctypes.data)
+    return out, int(nodes)
+
+
+def solve_tt(positions):
+    """(int16[P, 7] scores, nodes visited) of the same negamax with a transposition table: the checker below the stone counts
+    `solve` reaches.  Every position starts from an empty table, so a row and its node count do not depend on the batch."""
+    pos = _as_positions(positions)
+    out = np.zeros((len(pos), 7), dtype=np.int16)
+    nodes = ref_lib().solve_scores_tt(pos.ctypes.data, len(pos), out.ctypes.data)
+    if nodes == (1 << 64) - 1:
+        raise MemoryError("solve_scores_tt: no memory for its table")
     return out, int(nodes)
 
 
@@ -93,6 +106,36 @@ def playout_positions(seed: int, n: int, min_stones: int, max_stones: int = 41) 
                 cols = quiet or cols
             mask, value = play(mask, value, int(cols[rng.integers(len(cols))]))
     return np.array(out, dtype=np.uint64).reshape(-1, 2)
+
+
+class GoldenRows:
+    """tests/golden/solver_rows.npz (written by tests/golden/make_solver_rows.py, never by a test): positions of GOLDEN_L to 19 stones
+    and their score rows, the plain solver's from 14 stones up, the table solver's below.  Loaded once; the arrays are read-only."""
+
+    def __init__(self, z):
+        self.pos = np.stack([z["mask"], z["value"]], axis=1).astype(np.uint64)
+        self.stones, self.rows = z["stones"].astype(np.int64), z["row"].astype(np.int16)
+        self.ref = np.array([str(z["references"][i]) for i in z["ref"]])
+        self.ref_nodes = z["ref_nodes"].astype(np.uint64)
+        for a in (self.pos, self.stones, self.rows, self.ref, self.ref_nodes):
+            a.setflags(write=False)
+
+    def select(self, lo, hi, max_ref_nodes=None):
+        """(positions, rows) with lo..hi stones, in the file's order; max_ref_nodes: only those whose reference visited no more
+        nodes for the row -- the one way a test narrows its input."""
+        keep = (self.stones >= lo) & (self.stones <= hi)
+        if max_ref_nodes is not None:
+            keep &= self.ref_nodes <= np.uint64(max_ref_nodes)
+        return self.pos[keep], self.rows[keep]
+
+
+GOLDEN_L = 10      # the lowest stone count of the golden rows
+
+
+@functools.lru_cache(maxsize=None)
+def golden() -> GoldenRows:
+    with np.load(os.path.join(HERE, "golden", "solver_rows.npz"), allow_pickle=False) as z:
+        return GoldenRows(z)
 
 
 def kinds(positions, scores):

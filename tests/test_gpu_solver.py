@@ -1,7 +1,9 @@
 """The GPU solver (c4a0_amd.Solver: c4_solver_create / c4_solver_solve, c4a0_amd/csrc/c4_solver.hip) against the plain C solver
 (tests/solver_ref.c, pinned on the CPU by tests/test_solver_ref.py): exact equality of every score, under the default launch budget,
 a launch budget of 64 node visits, a table of 2^10 entries and a budget too small for some positions; the edge shapes; and
-`solver_score` of real results recomputed sample by sample.  Every Solver here has a table of at most 2^16 entries."""
+`solver_score` of real results recomputed sample by sample.  Every Solver here has a table of at most 2^16 entries.  20 stones is
+the floor of this file only, set by what the plain solver can do inside a test: tests/test_gpu_solver_low_stones.py goes on down to 12
+stones against recorded rows (tests/golden/solver_rows.npz)."""
 import functools
 import os
 import sys

@@ -1,6 +1,8 @@
 """Splitting and the book of the GPU solver (c4a0_amd.Solver(book_entries=...), solve(split_stones=...): c4_solver_solve_ex,
 c4a0_amd/csrc/c4_solver_split.hpp, solver_kernel<true>) against the plain C solver (tests/solver_ref.c): 300 positions of 24 stones
-under a budget of 64 node visits per task, which alone solves only part of them.  Every table here has at most 2^16 entries."""
+under a budget of 64 node visits per task, which alone solves only part of them.  Every table here has at most 2^16 entries.
+Splitting and the book at the stone counts they are meant for, 12 to 14, are in tests/test_gpu_solver_low_stones.py, against the
+recorded rows of tests/golden/solver_rows.npz."""
 import functools
 import os
 import sys

@@ -1,5 +1,6 @@
 """The plain C solver (tests/solver_ref.c), the checker of the GPU solver, pinned on the CPU: against a pruning-free brute force in
-the same file, on hand-checkable positions, and Solution::score_policy (reference rust/src/solver.rs:201-228) against the
+the same file, on hand-checkable positions; its variant with a transposition table (solve_tt, which writes the recorded rows below 14
+stones) against both; and Solution::score_policy (reference rust/src/solver.rs:201-228) against the
 product's host arithmetic on given score rows (c4a0_amd.solver.score_rows).  No GPU needed."""
 import os
 import sys
@@ -24,6 +25,48 @@ def test_alpha_beta_equals_brute_force():
     k = R.kinds(pos, got)
     assert min(k.values()) > 0, k          # the set has immediate wins, full columns, 41 stones, single legal moves
     assert (got[got != FULL_COLUMN] != 0).any() and (got == 0).any()
+
+
+def test_table_solver_equals_brute_force():
+    """solve_tt, the checker of the stone counts `solve` cannot reach, on the set of (a): its table changes no score."""
+    pos = R.playout_positions(7, 400, 32)
+    got, nodes = R.solve_tt(pos)
+    assert np.array_equal(got, R.brute(pos)) and 0 < nodes <= R.solve(pos)[1]
+
+
+def test_table_solver_equals_plain_solver_from_20_stones():
+    """The 2 000 positions of 20 or more stones the GPU tests use (tests/test_gpu_solver.py): the plain solver takes about 5 s."""
+    pos = R.playout_positions(20261019, 2000, 20)
+    want, plain_nodes = R.solve(pos)
+    got, nodes = R.solve_tt(pos)
+    assert np.array_equal(got, want)
+    assert nodes < plain_nodes                                        # measured: 7 773 314 against 111 567 507
+    # a row and its node count depend on nothing solved before it: one at a time, in another order, the same
+    one_by_one = [R.solve_tt(pos[i:i + 1]) for i in (1999, 7, 0)]
+    assert np.array_equal(np.concatenate([r for r, _ in one_by_one]), want[[1999, 7, 0]])
+    assert sum(n for _, n in one_by_one) == sum(R.solve_tt(pos[[i]])[1] for i in (0, 7, 1999))
+    assert R.solve_tt(pos[:50])[1] == sum(R.solve_tt(pos[i:i + 1])[1] for i in range(50))
+
+
+@pytest.mark.slow
+def test_table_solver_equals_plain_solver_at_16_stones():
+    """24 positions of 16 stones: about 25 s of plain solver, scores up to +-13."""
+    pos = R.playout_positions(77 + 16, 24, 16, 16)
+    want, _ = R.solve(pos)
+    got, _ = R.solve_tt(pos)
+    assert np.array_equal(got, want)
+    assert np.abs(want[want != FULL_COLUMN]).max() == 13
+
+
+def test_table_solver_edges():
+    assert np.array_equal(R.solve_tt([R.from_moves([2, 2, 3, 3, 4])])[0], R.solve([R.from_moves([2, 2, 3, 3, 4])])[0])
+    pos = R.playout_positions(13, 200, 28)
+    rows, _ = R.solve_tt(pos)
+    mirrored = np.array([R.mirror(m, v) for m, v in pos.tolist()], dtype=np.uint64)
+    assert np.array_equal(R.solve_tt(mirrored)[0], rows[:, ::-1]) and np.array_equal(rows, R.solve(pos)[0])
+    late = R.playout_positions(11, 40, 41)
+    assert np.array_equal(R.solve_tt(late)[0], R.brute(late))
+    assert R.solve_tt(np.zeros((0, 2), np.uint64))[0].shape == (0, 7)
 
 
 def test_immediate_win_scores_43_minus_s_halved():

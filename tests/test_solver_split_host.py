@@ -1,8 +1,9 @@
 """The solver's scheduler and book (c4a0_amd/csrc/c4_solver_split.hpp) on the CPU: tests/solver_split_host.cpp gives it a "launch"
 that loops over the Lane::step the kernel runs, and the plain C solver (tests/solver_ref.c) says what every row must be.  Splitting
 at a budget of 64 node visits, the cap on split tasks, the book (canonical keys, export and import, a second solve without a launch,
-a book that fills up, invalid entries refused by index), and the same driver once more as a stand-alone program under
-AddressSanitizer and UBSan.  No GPU needed."""
+a book that fills up, invalid entries refused by index) on positions of 24 stones, which the plain solver solves inside the test;
+splitting and the book once more at 12 and 13 stones, where they are meant to be used, against the recorded rows of
+tests/golden/solver_rows.npz; and the same driver as a stand-alone program under AddressSanitizer and UBSan.  No GPU needed."""
 import ctypes as C
 import functools
 import os
@@ -164,6 +165,30 @@ def test_book_round_trip_and_a_second_solve_without_a_launch():
     assert solved.all() and np.array_equal(got, R.solve(up)[0])
     a.close()
     b.close()
+
+
+def test_splitting_and_the_book_at_12_and_13_stones_against_golden_rows():
+    """The stone counts the book and `split_stones=14` are meant for, against the recorded rows (tests/golden/solver_rows.npz): scores to
+    +-15 in the book's bytes.  Measured with a table of 2^20 entries: under 3 * 2^19 visits a task, two 13-stone tasks of the 48 positions
+    run out and split into 7 tasks of 14 stones, which may not split and all finish (189 tasks, 23.8 M visits, 237 book entries, 5 s);
+    under 2^20 visits two 14-stone tasks do not finish, under 2^22 nothing splits."""
+    pos, want = R.golden().select(12, 13)
+    assert len(pos) == 48
+    e = Emu(log2_entries=20, book_entries=1 << 17)
+    budget = dict(nodes_per_launch=1 << 30, max_nodes=3 << 19, split_stones=14)
+    got, solved, stats = e.solve(pos, **budget)
+    print(stats)
+    assert solved.all() and stats["unsolved_tasks"] == 0 and np.array_equal(got, want)
+    assert stats["split_tasks"] > 0 and stats["combined_nodes"] > 0
+    assert stats["book_inserts"] > len(pos) and stats["book_full"] == 0 and len(e.book()) == stats["book_inserts"]
+    scores_in_book = (e.book() >> np.uint64(56)).astype(np.int64) - 32
+    assert scores_in_book.max() >= 13 and scores_in_book.min() <= -13        # beyond any score of a 20-stone position
+    got, solved, stats = e.solve(pos, **budget)
+    assert stats["launches"] == 0 and stats["tasks"] == 0 and stats["book_hits_host"] > 0 and solved.all() and np.array_equal(got, want)
+    mirrored = np.array([R.mirror(m, v) for m, v in pos.tolist()], dtype=np.uint64)
+    got, solved, stats = e.solve(mirrored, **budget)
+    assert stats["launches"] == 0 and np.array_equal(got, want[:, ::-1])
+    e.close()
 
 
 def test_a_book_of_16_entries_fills_up_and_the_scores_stay_exact():
