@@ -196,6 +196,10 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp]),
     "c4_train_linear_dgrad_f32": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "c4_train_linear_wgrad_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "c4_train_cast_bf16": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    "c4_train_bn_relu_fwd_bf16": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    "c4_train_bn_relu_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "c4_quantize_bf16_fp8": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _vp]),
     "c4_linear_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                 C.c_uint32, _vp]),

@@ -6,6 +6,11 @@ the default network are over 90 % of a training step's FLOPs.  `HiddenBlockFunct
 `c4_train_linear_wgrad_f32` (c4a0_amd/csrc/c4_train.hip); `forward_train` walks the unchanged module tree of `c4a0_amd.nn.ConnectFourNet`
 and sends its hidden triples through it.  The tower, the two output layers, log-softmax, tanh and the loss stay stock PyTorch
 autograd: that is plumbing.
+
+heads="bf16" (opt-in) runs the same triples in bf16 mixed precision: `HiddenBlockBf16Function` rounds x and the f32 master weights to
+bf16, takes all three products of a step -- forward x W^T, dgrad dz W, wgrad dz^T x -- from the bf16 MFMA GEMM `c4_linear_bf16`, and the
+batch norm, the casts and the transposes the GEMM's k-major operands need from c4a0_amd/csrc/c4_train_bf16.hip.  Where it rounds is
+include/c4a0_hip.h's "bf16 mixed-precision training"; parameters, gradients, Adam and the running statistics stay f32.
 """
 from __future__ import annotations
 
@@ -16,7 +21,7 @@ import torch.nn as nn
 
 from ._lib import check, lib
 
-HEADS = ("auto", "hip", "torch")
+HEADS = ("auto", "hip", "torch", "bf16")
 
 
 def _stream(device: torch.device) -> int:
@@ -77,14 +82,115 @@ class HiddenBlockFunction(torch.autograd.Function):
         return dx, dw, db, dgamma, dbeta, None
 
 
-def hidden_block(block: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+def _rows8(t: torch.Tensor) -> torch.Tensor:
+    """`t` as the bf16 kernels read a matrix: unit column stride, row stride a multiple of 8, 16-byte aligned (else a dense copy)."""
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous()
+
+
+def _cast_bf16(src: torch.Tensor, dst: bool, dst_t: bool):
+    """c4_train_cast_bf16 of an f32 or bf16 matrix [m][c]: (bf16 [m][c] or None, the transpose bf16 [c][64 ceil(m / 64)], its pad
+    columns zeros, or None)."""
+    m, c = src.shape
+    mp = 64 * ((m + 63) // 64)
+    out = torch.empty((m, c), dtype=torch.bfloat16, device=src.device) if dst else None
+    out_t = torch.empty((c, mp), dtype=torch.bfloat16, device=src.device) if dst_t else None
+    check(lib().c4_train_cast_bf16(src.data_ptr(), int(src.dtype == torch.bfloat16), m, c, src.stride(0), out.data_ptr() if dst else None, c,
+                                   out_t.data_ptr() if dst_t else None, mp, _stream(src.device)))
+    return out, out_t
+
+
+def _linear_bf16(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, m: int, n: int, k: int) -> torch.Tensor:
+    """bf16(x[:m, :k] w[:n, :k]^T + bias) [m][n] by c4_linear_bf16, the tile configuration automatic"""
+    y = torch.empty((m, n), dtype=torch.bfloat16, device=x.device)
+    check(lib().c4_linear_bf16(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), m, n, k, x.stride(0), n, 0, 0, _stream(x.device)))
+    return y
+
+
+class HiddenBlockBf16Function(torch.autograd.Function):
+    """y = bf16(relu(batch_norm(bf16(bf16(x) bf16(W)^T + b)))) with batch statistics: the block in bf16 mixed precision, rounded where
+    include/c4a0_hip.h's "bf16 mixed-precision training" says and nowhere else.  x is f32 (the first block of a head) or bf16 (a
+    chained block, with `x_t`, the previous block's zero-padded y^T, if it made one); the parameters are f32.  Returns (y, y_t, mean,
+    var): y bf16, y_t its transpose for the next block (None unless `emit_t`), mean and the BIASED variance of z in f32, not
+    differentiable.  Saves xb, xb_t, Wb, z, mean, var, gamma and beta; the backward recomputes the pre-activation from z.  All
+    three products are c4_linear_bf16: dgrad reads Wb^T [k][n], wgrad dz^T [n][mp] and xb^T [k][mp] with the batch as its k."""
+
+    @staticmethod
+    def forward(ctx, x, x_t, weight, bias, gamma, beta, eps: float, emit_t: bool):
+        m, (n, k) = x.shape[0], weight.shape
+        if m < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        L, dev = lib(), x.device
+        mp = 64 * ((m + 63) // 64)
+        ctx.x_dtype = x.dtype
+        if x.dtype not in (torch.float32, torch.bfloat16) or x.device.type != "cuda" or any(t.dtype != torch.float32 for t in (weight, bias, gamma, beta)):
+            raise ValueError(f"the bf16 block takes an f32 or bf16 input on a HIP device and f32 parameters, not {x.dtype} on {x.device}")
+        if x.dtype == torch.bfloat16:
+            xb = _rows8(x)
+            xb_t = x_t if x_t is not None and tuple(x_t.shape) == (k, mp) else _cast_bf16(xb, False, True)[1]
+        else:
+            xb, xb_t = _cast_bf16(_rows8(x), True, True)
+        wb = _cast_bf16(weight.contiguous(), True, False)[0]
+        z = _linear_bf16(xb, wb, bias, m, n, k)
+        y = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+        y_t = torch.empty((n, mp), dtype=torch.bfloat16, device=dev) if emit_t else None
+        mean = torch.empty(n, dtype=torch.float32, device=dev)
+        var = torch.empty(n, dtype=torch.float32, device=dev)
+        check(L.c4_train_bn_relu_fwd_bf16(z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, m, n, n, n, y.data_ptr(), mean.data_ptr(),
+                                          var.data_ptr(), y_t.data_ptr() if emit_t else None, mp, _stream(dev)))
+        ctx.save_for_backward(xb, xb_t, wb, z, mean, var, gamma, beta)
+        ctx.eps = eps
+        if emit_t:
+            ctx.mark_non_differentiable(y_t, mean, var)
+        else:
+            ctx.mark_non_differentiable(mean, var)
+        return y, y_t, mean, var
+
+    @staticmethod
+    def backward(ctx, dy, _dy_t, _dmean, _dvar):
+        xb, xb_t, wb, z, mean, var, gamma, beta = ctx.saved_tensors
+        m, (n, k) = xb.shape[0], wb.shape
+        L, dev = lib(), xb.device
+        mp = xb_t.shape[1]
+        dy = _rows8(dy) if dy.dtype == torch.bfloat16 else _cast_bf16(_rows8(dy.float()), True, False)[0]
+        dz = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+        dz_t = torch.empty((n, mp), dtype=torch.bfloat16, device=dev)
+        dgamma = torch.empty(n, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(n, dtype=torch.float32, device=dev)
+        db = torch.empty(n, dtype=torch.float32, device=dev)
+        check(L.c4_train_bn_relu_bwd_bf16(dy.data_ptr(), z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ctx.eps,
+                                          m, n, dy.stride(0), n, n, dz.data_ptr(), dz_t.data_ptr(), mp, dgamma.data_ptr(), dbeta.data_ptr(),
+                                          db.data_ptr(), _stream(dev)))
+        zeros = torch.zeros(max(n, k), dtype=torch.float32, device=dev)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            wb_t = _cast_bf16(wb, False, True)[1]                  # [k][n]: n % 64 == 0, no pad
+            dx = _linear_bf16(dz, wb_t, zeros, m, k, n).to(ctx.x_dtype)
+        dw = _linear_bf16(dz_t, xb_t, zeros, n, k, mp).float()
+        return dx, None, dw, db, dgamma, dbeta, None, None
+
+
+def hidden_block(block: nn.Sequential, x: torch.Tensor, path: str = "hip", emit_t: bool = False) -> torch.Tensor:
     """One `Sequential(Linear, BatchNorm1d, ReLU)` on the HIP kernels.  Train mode: batch statistics, and the running statistics
     move exactly as `nn.BatchNorm1d` moves them (momentum 0.1, the UNBIASED variance var m / (m - 1), num_batches_tracked += 1).
-    Eval mode: the module's own forward."""
+    Eval mode: the module's own forward.  path="hip": f32 in, f32 out (HiddenBlockFunction).  path="bf16": f32 or bf16 in, bf16 out
+    (HiddenBlockBf16Function); with emit_t the block also writes y^T and hands it to a following block (as `y.c4_transposed`), which
+    then needs no cast launch of its own."""
     lin, bn = block[0], block[1]
+    if path not in ("hip", "bf16"):
+        raise ValueError(f'path must be "hip" or "bf16", not {path!r}')
     if not bn.training:
+        if path == "bf16":
+            raise ValueError('heads="bf16": the block is in eval mode (the kernels are the train-mode block)')
         return block(x)
-    y, mean, var = HiddenBlockFunction.apply(x, lin.weight, lin.bias, bn.weight, bn.bias, bn.eps)
+    if path == "bf16":
+        y, y_t, mean, var = HiddenBlockBf16Function.apply(x, getattr(x, "c4_transposed", None), lin.weight, lin.bias, bn.weight, bn.bias, bn.eps,
+                                                          emit_t)
+        if emit_t:
+            y.c4_transposed = y_t
+    else:
+        y, mean, var = HiddenBlockFunction.apply(x, lin.weight, lin.bias, bn.weight, bn.bias, bn.eps)
     if bn.track_running_stats and bn.running_mean is not None:
         m = x.shape[0]
         with torch.no_grad():
@@ -95,14 +201,16 @@ def hidden_block(block: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-def hip_refusal(model: nn.Module, planes: Optional[torch.Tensor] = None) -> Optional[str]:
-    """Why `model` (and `planes`) cannot take the "hip" path, or None if it can."""
+def hip_refusal(model: nn.Module, planes: Optional[torch.Tensor] = None, path: str = "hip") -> Optional[str]:
+    """Why `model` (and `planes`) cannot take the "hip" path (or, path="bf16", the bf16 one), or None if it can."""
     p = next(model.parameters())
     if p.device.type != "cuda":
         return f"the model is on {p.device}, not on a HIP device"
     if any(q.dtype != torch.float32 for q in model.parameters()):
-        return f"the model is {p.dtype}, the kernels are f32"
+        return f"the model is {p.dtype}, the kernels are f32" if path == "hip" else f"the model is {p.dtype}, the master parameters must be f32"
     c = model.config.conv_filter_size
+    if path == "bf16" and c % 32:
+        return f"conv_filter_size {c} is not a multiple of 32 (c4_linear_bf16 needs F = 42 C to be a multiple of 192)"
     if c % 16:
         return f"conv_filter_size {c} is not a multiple of 16 (F = 42 C must be a multiple of 32)"
     if not model.training:
@@ -119,32 +227,39 @@ AUTO_HEADS = "torch"
 
 
 def resolve_heads(model: nn.Module, heads: str = "auto", planes: Optional[torch.Tensor] = None) -> str:
-    """"hip" or "torch".  heads="hip" raises ValueError naming the reason where the kernels cannot run; "auto" takes "torch" there."""
+    """"hip", "bf16" or "torch".  heads="hip" and heads="bf16" raise ValueError naming the reason where the kernels cannot run; "auto"
+    takes "torch" there.  "bf16" is opt-in: "auto" never resolves to it."""
     if heads not in HEADS:
         raise ValueError(f"heads must be one of {HEADS}, not {heads!r}")
     if heads == "torch":
         return "torch"
-    why = hip_refusal(model, planes)
-    if heads == "hip":
+    why = hip_refusal(model, planes, "bf16" if heads == "bf16" else "hip")
+    if heads in ("hip", "bf16"):
         if why is not None:
-            raise ValueError(f'heads="hip": {why}')
-        return "hip"
+            raise ValueError(f'heads="{heads}": {why}')
+        return heads
     return "torch" if why is not None else AUTO_HEADS
 
 
-def _head(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
-    for layer in seq:
-        x = hidden_block(layer, x) if isinstance(layer, nn.Sequential) else layer(x)
+def _head(seq: nn.Sequential, x: torch.Tensor, path: str = "hip") -> torch.Tensor:
+    layers = list(seq)
+    for i, layer in enumerate(layers):
+        if isinstance(layer, nn.Sequential):
+            # a bf16 block that feeds another writes its y^T too: the next block's wgrad operand, without a cast launch
+            x = hidden_block(layer, x, path, emit_t=path == "bf16" and i + 1 < len(layers) and isinstance(layers[i + 1], nn.Sequential))
+        else:
+            x = layer(x.float() if x.dtype == torch.bfloat16 else x)   # the f32 output layer: autograd rounds its dx back to bf16
     return x
 
 
 def forward_train(model: nn.Module, planes: torch.Tensor, heads: str = "auto") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """`model(planes)` -- (policy log-probabilities [B, 7], q_penalty [B], q_no_penalty [B]) -- with autograd, the hidden triples of
     both heads on the HIP kernels where heads resolves to "hip" (an f32 model in train mode on a HIP device whose conv_filter_size is a
-    multiple of 16), else the plain module forward."""
-    if resolve_heads(model, heads, planes) == "torch":
+    multiple of 16) or to "bf16" (the same, a multiple of 32; bf16 mixed precision), else the plain module forward."""
+    path = resolve_heads(model, heads, planes)
+    if path == "torch":
         return model(planes)
     x = model.conv(planes)
     x = x.reshape(x.shape[0], -1)
-    q = _head(model.fc_value, x)
-    return _head(model.fc_policy, x), q[:, 0], q[:, 1]
+    q = _head(model.fc_value, x, path)
+    return _head(model.fc_policy, x, path), q[:, 0], q[:, 1]

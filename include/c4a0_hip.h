@@ -850,6 +850,53 @@ int c4_train_linear_dgrad_f32(const float* dz_dev, const float* w_dev, float* dx
 int c4_train_linear_wgrad_f32(const float* dz_dev, const float* x_dev, float* dw_dev, float* db_dev, uint32_t m, uint32_t n, uint32_t k,
                               uint32_t ldz, uint32_t ldx, void* stream);
 
+/* ---- bf16 mixed-precision training of the hidden blocks (c4a0_amd/train_heads.py heads="bf16"; added functions only: C4_ABI_VERSION
+ * stays what it was): where a block rounds.  Parameters, optimiser state and running statistics stay f32.  Every rounding to bf16 is
+ * round to nearest, ties to even (v_cvt_pk_bf16_f32); a value is rounded at the points below and nowhere else; all accumulation is
+ * f32.  tests/train_bf16_ref.py restates this in float64 with a bf16 rounding in integer arithmetic at exactly these points.
+ * Forward
+ *   1. xb = bf16(x) when the block's input is f32 (the first block of a head, fed by the tower); a bf16 input is taken as it is;
+ *   2. Wb = bf16(W) from the f32 master weights, every step;
+ *   3. z = bf16(acc + b): c4_linear_bf16 with relu = 0, the f32 bias passed as it is, not rounded;
+ *   4. mean, var (biased): f32 over z widened exactly, two passes (sum z / m, then sum (z - mean)^2 / m);
+ *   5. pre = ((z - mean) * rstd) * gamma + beta in f32, rstd = 1 / sqrt(var + eps);
+ *   6. y = bf16(relu(pre)); ReLU's predicate is !(pre <= 0), as in the f32 kernels: a NaN passes.
+ * Backward, from dy in bf16 (an f32 dy is rounded once)
+ *   1. g = dy where the pre-activation, recomputed by the forward's operations, passes the predicate, else 0;
+ *   2. dbeta = sum_r g, dgamma = sum_r g xh, f32, xh = ((z - mean) - corr) * rstd with corr the mean of the deviations z - mean
+ *      (c4_train_bn_relu_bwd_f32's corrected deviations);
+ *   3. dz32 = gamma rstd ((g - dbeta / m) - xh dgamma / m), evaluated as (gamma rstd / m) ((m g - dbeta) - xh dgamma): m g is exact for a
+ *      bf16 g, where g - fl(dbeta / m) would round every row of a binade the same way;
+ *   4. db = sum_r dz32 in f32, from the values before the rounding: (gamma rstd / m) sum_r ((m g - dbeta) - xh dgamma), the column's
+ *      factor applied once, after the sum, and the rounding error of every m g - dbeta (TwoSum gives it exactly; it is the same in every
+ *      row of a binade, and no row can carry it) summed beside the rounded values: db is 0 in real numbers, and what is left is
+ *      dbeta's own rounding.  The sum is kept two-fold (every addition's rounding error carried along): its summands cancel;
+ *   5. dz = bf16(dz32);
+ *   6. dx = bf16(sum_j dz[r][j] Wb[j][c]):  c4_linear_bf16(x = dz [m][n], w = Wb^T [k][n], zero bias);
+ *   7. dw = bf16(sum_r dz[r][j] xb[r][c]):  c4_linear_bf16(x = dz^T [n][mp], w = xb^T [k][mp], zero bias), mp = 64 ceil(m / 64), the pad
+ *      columns exact zeros; widened exactly to f32 for the parameter's gradient.
+ * Every sum has one order that the shape alone decides, there are no atomics: two calls give the same bytes.  Non-finite input: a
+ * column of z that holds a NaN or an infinity, or whose sum overflows, poisons that column's y, dz, dgamma and db; dbeta is the column
+ * sum of dy; no other column changes.  A pad row or column is a selected zero, never a product with zero.
+ * The calls below: n % 192 == 0 (what c4_linear_bf16 needs), leading dimensions multiples of 8 and at least the row length, arrays
+ * 16-byte aligned, operands below 2^31 elements; a violation is C4_ERR_BAD_ARG with a c4_last_error_string and nothing is launched.
+ * No synchronisation: capturable. */
+
+/* src [m][lds] (c columns; f32, or bf16 where src_is_bf16 != 0) -> dst bf16 [m][ldd] and / or its transpose dst_t bf16 [c][ldt]
+ * (either may be NULL, not both).  ldt >= 64 ceil(m / 64); columns m .. ldt - 1 of every row of dst_t are written as zeros.  A bf16
+ * source is copied bit for bit.  c % 16 == 0, m >= 1. */
+int c4_train_cast_bf16(const void* src_dev, uint32_t src_is_bf16, uint32_t m, uint32_t c, uint32_t lds, void* dst_dev /*bf16 [m][ldd]*/,
+                       uint32_t ldd, void* dst_t_dev /*bf16 [c][ldt]*/, uint32_t ldt, void* stream);
+/* Steps 4-6 of the forward: z bf16 [m][ldz] -> y bf16 [m][ldy], mean and var f32 [n]; y_t (may be NULL) bf16 [n][ldt] receives the
+ * transpose of y, zero-padded as dst_t above.  m >= 2. */
+int c4_train_bn_relu_fwd_bf16(const void* z_dev, const float* gamma_dev, const float* beta_dev, float eps, uint32_t m, uint32_t n, uint32_t ldz,
+                              uint32_t ldy, void* y_dev, float* mean_dev, float* var_dev, void* y_t_dev, uint32_t ldt, void* stream);
+/* Steps 1-5 of the backward: dy bf16 [m][lddy], z bf16 [m][ldz], the mean and var of the call above -> dz bf16 [m][lddz], its
+ * zero-padded transpose dz_t bf16 [n][ldt], dgamma, dbeta and db f32 [n].  m >= 2. */
+int c4_train_bn_relu_bwd_bf16(const void* dy_dev, const void* z_dev, const float* mean_dev, const float* var_dev, const float* gamma_dev,
+                              const float* beta_dev, float eps, uint32_t m, uint32_t n, uint32_t lddy, uint32_t ldz, uint32_t lddz, void* dz_dev,
+                              void* dz_t_dev, uint32_t ldt, float* dgamma_dev, float* dbeta_dev, float* db_dev, void* stream);
+
 /* ---- exact solver ----------------------------------------------------------------------------------------------------------
  * What the reference gets from Pascal Pons' c4solver binary, its opening book and a rocksdb cache (rust/src/solver.rs): here a HIP
  * alpha-beta search with no binary, no book and no database.  These calls only ADD functions: C4_ABI_VERSION stays what it was.

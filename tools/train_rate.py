@@ -11,6 +11,10 @@
     is the faster of the two in the recorded file.
 (c) One default-shaped generation through train_single_gen (1 700 games, n = 1 400, batch 2 000; --max-epochs, default 10, instead
     of the reference's 100 so that the run stays short: train_s scales with the epochs run): wall seconds of play / split / train.
+(d) --bf16: the opt-in heads="bf16" path alone -> profiles/train_rate_bf16.json.  At the same shape every kernel of c4_train_bf16.hip
+    and each of the three c4_linear_bf16 products (forward, dgrad, wgrad) beside the stock op on the same tensors; one hidden block
+    forward + backward and the whole optimiser step with heads="bf16", heads="torch" and torch.autocast(bfloat16) on the stock module
+    (autocast also runs the tower's convolutions in bf16, which heads="bf16" does not), each callable timed in turn, medians of 7 rounds.
 Speed is recorded here, never asserted in a test."""
 import ctypes as C
 import json
@@ -111,6 +115,122 @@ def whole_step():
             "hip_range_ms": [v * 1e-3 for v in r["hip_range_us"]], "torch_range_ms": [v * 1e-3 for v in r["torch_range_us"]]}
 
 
+def alternating(fns: dict, pairs=7, launches=20):
+    """medians (us per call) of `pairs` rounds that time every callable of `fns` in turn, and their spreads"""
+    for _ in range(3):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name in fns}
+    for _ in range(pairs):
+        for name, fn in fns.items():
+            t[name].append(time_us(fn, launches))
+    return {name: {"us": statistics.median(v), "range_us": [min(v), max(v)]} for name, v in t.items()}
+
+
+def bf16_leg():
+    """heads="bf16" at m = 2 000, F = 1 344: every kernel of c4_train_bf16.hip and each of the three c4_linear_bf16 products alone (beside
+    the stock op that does the same job on the same tensors), one hidden block forward + backward and the whole optimiser step with
+    heads="bf16", heads="torch" and torch.autocast(bfloat16) on the stock module."""
+    from c4a0_amd import training as T
+    from c4a0_amd.nn import ConnectFourNet, ModelConfig
+    from c4a0_amd.train_heads import forward_train, hidden_block
+
+    L, ck = _lib.lib(), _lib.check
+    g = torch.Generator().manual_seed(0)
+    m, n, k = M, FEAT, FEAT
+    mp = 64 * ((m + 63) // 64)
+    bf = torch.bfloat16
+    x, dy32 = (torch.randn(m, FEAT, generator=g).to(dev) for _ in range(2))
+    w = (torch.randn(n, k, generator=g) / k ** 0.5).to(dev)
+    b, gamma, beta = torch.randn(n, generator=g).to(dev), (torch.rand(n, generator=g) + 0.5).to(dev), torch.randn(n, generator=g).to(dev)
+    zeros = torch.zeros(n, device=dev)
+    xb, wb, z, y, dz, dx, dyb = (torch.empty((m, n), dtype=bf, device=dev) for _ in range(7))
+    wb = torch.empty((n, k), dtype=bf, device=dev)
+    xb_t, dz_t, y_t = (torch.empty((n, mp), dtype=bf, device=dev) for _ in range(3))
+    wb_t, dw = torch.empty((k, n), dtype=bf, device=dev), torch.empty((n, k), dtype=bf, device=dev)
+    mean, var, db, dgamma, dbeta = (torch.empty(n, device=dev) for _ in range(5))
+    dyb.copy_(dy32)
+
+    def linear(xo, wo, bias, yo, mm, nn, kk):
+        ck(L.c4_linear_bf16(p(xo), p(wo), p(bias), p(yo), mm, nn, kk, xo.stride(0), nn, 0, 0, stream()))
+
+    cast_x = lambda: ck(L.c4_train_cast_bf16(p(x), 0, m, k, k, p(xb), k, p(xb_t), mp, stream()))
+    cast_w = lambda: ck(L.c4_train_cast_bf16(p(w), 0, n, k, k, p(wb), k, None, 0, stream()))
+    cast_wt = lambda: ck(L.c4_train_cast_bf16(p(wb), 1, n, k, k, None, 0, p(wb_t), n, stream()))
+    fwd = lambda: linear(xb, wb, b, z, m, n, k)
+    bn_fwd = lambda: ck(L.c4_train_bn_relu_fwd_bf16(p(z), p(gamma), p(beta), EPS, m, n, n, n, p(y), p(mean), p(var), p(y_t), mp, stream()))
+    bn_bwd = lambda: ck(L.c4_train_bn_relu_bwd_bf16(p(dyb), p(z), p(mean), p(var), p(gamma), p(beta), EPS, m, n, n, n, n, p(dz), p(dz_t), mp, p(dgamma),
+                                                    p(dbeta), p(db), stream()))
+    for fn in (cast_x, cast_w, cast_wt, fwd, bn_fwd, bn_bwd):      # every operand of the timed calls is a real one
+        fn()
+    zt, gt, bt = z.float().requires_grad_(), gamma.clone().requires_grad_(), beta.clone().requires_grad_()
+    yt = torch.relu(F.batch_norm(zt, None, None, gt, bt, True, 0.1, EPS))
+    bb = b.to(bf)
+    out = {"kernels": {
+        "cast_x_and_transpose": alternating({"hip": cast_x, "torch": lambda: (x.to(bf), x.to(bf).t().contiguous())}),
+        "cast_w": alternating({"hip": cast_w, "torch": lambda: w.to(bf)}),
+        "transpose_w": alternating({"hip": cast_wt, "torch": lambda: wb.t().contiguous()}),
+        "linear_fwd": alternating({"hip": fwd, "torch": lambda: F.linear(xb, wb, bb)}),
+        "dgrad": alternating({"hip": lambda: linear(dz, wb_t, zeros, dx, m, k, n), "torch": lambda: dz @ wb}),
+        "wgrad": alternating({"hip": lambda: linear(dz_t, xb_t, zeros, dw, n, k, mp), "torch": lambda: dz.t() @ xb}),
+        "bn_relu_fwd": alternating({"hip": bn_fwd, "torch_f32": lambda: torch.relu(F.batch_norm(zt.detach(), None, None, gamma, beta, True, 0.1, EPS))}),
+        "bn_relu_bwd": alternating({"hip": bn_bwd, "torch_f32": lambda: torch.autograd.grad(yt, (zt, gt, bt), dy32, retain_graph=True)}),
+    }}
+    flop = 2.0 * m * n * k
+    for name in ("linear_fwd", "dgrad", "wgrad"):
+        for side in out["kernels"][name].values():
+            side["tflops"] = flop / side["us"] * 1e-6
+
+    # one hidden block, forward + backward (dx included), and the whole optimiser step
+    def block_fn(kind):
+        torch.manual_seed(0)
+        block = torch.nn.Sequential(torch.nn.Linear(FEAT, FEAT), torch.nn.BatchNorm1d(FEAT), torch.nn.ReLU()).to(dev).train()
+        xin = x.clone().requires_grad_()
+
+        def run():
+            xin.grad = None
+            block.zero_grad(set_to_none=True)
+            if kind == "bf16":
+                hidden_block(block, xin, "bf16").backward(dyb)
+            elif kind == "torch":
+                block(xin).backward(dy32)
+            else:
+                with torch.autocast("cuda", dtype=bf):
+                    yy = block(xin)
+                yy.backward(dy32.to(yy.dtype))
+
+        return run
+
+    out["hidden_block_fwd_bwd"] = alternating({kind: block_fn(kind) for kind in ("bf16", "torch", "autocast")}, launches=10)
+    g = torch.Generator().manual_seed(1)
+    cell = torch.randint(0, 3, (M, 6, 7), generator=g)
+    batch = (torch.stack([cell == 1, cell == 2], 1).float().to(dev), torch.softmax(torch.randn(M, 7, generator=g), 1).to(dev),
+             (torch.rand(M, generator=g) * 2 - 1).to(dev), (torch.rand(M, generator=g) * 2 - 1).to(dev))
+
+    def step_fn(kind):
+        torch.manual_seed(0)
+        model = ConnectFourNet(ModelConfig(1, 32, 4, 2)).to(dev).train()
+        opt = torch.optim.Adam(model.parameters(), lr=2e-3, weight_decay=4e-4)
+
+        def run():
+            opt.zero_grad(set_to_none=True)
+            if kind == "autocast":
+                with torch.autocast("cuda", dtype=bf):
+                    res = model(batch[0])
+                res = tuple(t.float() for t in res)
+            else:
+                res = forward_train(model, batch[0], kind)
+            T.loss(res, batch)[0].backward()
+            opt.step()
+
+        return run
+
+    out["step"] = alternating({kind: step_fn(kind) for kind in ("bf16", "torch", "autocast")}, launches=5)
+    out["step"].update(batch=M, model=[1, 32, 4, 2])
+    return out
+
+
 def generation(max_epochs: int, heads: str):
     from c4a0_amd import training as T
     from c4a0_amd.nn import ModelConfig
@@ -131,8 +251,20 @@ def main():
     ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "train_rate.json"))
     ap.add_argument("--no-generation", action="store_true")
     ap.add_argument("--max-epochs", type=int, default=10)
+    ap.add_argument("--bf16", action="store_true", help='the heads="bf16" leg alone -> profiles/train_rate_bf16.json')
     a = ap.parse_args()
     out_path, max_epochs = a.out, a.max_epochs
+    if a.bf16:
+        if out_path == ap.get_default("out"):
+            out_path = os.path.join(ROOT, "profiles", "train_rate_bf16.json")
+        res = {"device": torch.cuda.get_device_name(0), "shape": {"m": M, "n": FEAT, "k": FEAT}}
+        res.update(bf16_leg())
+        print(json.dumps(res, indent=1), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     res = {"device": torch.cuda.get_device_name(0), "shape": {"m": M, "n": FEAT, "k": FEAT}, "kernels": kernels(), "step": whole_step()}
     print(json.dumps(res, indent=1), flush=True)
     if not a.no_generation:
