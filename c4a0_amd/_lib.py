@@ -114,6 +114,14 @@ class SolverOptions(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("struct_size", "nodes_per_launch", "max_nodes_per_position", "split_stones", "split_max_tasks")]
 
 
+class AdamSegment(C.Structure):
+    """include/c4a0_hip.h c4_adam_segment."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_uint64), ("first_block", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+ADAM_BLOCK_ELEMS = 4096   # include/c4a0_hip.h C4_ADAM_BLOCK_ELEMS == c4_train_adam_block_elems()
+
 SOLVE_FULL_COLUMN, SOLVE_UNSOLVED = -1000, -32768   # include/c4a0_hip.h C4_SOLVE_FULL_COLUMN, C4_SOLVE_UNSOLVED
 SOLVER_TT_ENTRIES = 1 << 24                         # C4_SOLVER_TT_ENTRIES
 
@@ -200,6 +208,8 @@ SIGNATURES = {
     "c4_train_bn_relu_fwd_bf16": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "c4_train_bn_relu_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                             _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "c4_train_adam_f32": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    "c4_train_adam_block_elems": (C.c_int, []),
     "c4_quantize_bf16_fp8": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _vp]),
     "c4_linear_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                 C.c_uint32, _vp]),

@@ -92,8 +92,84 @@ def evaluate_loss(model, data, batch_size: int) -> float:
     return total / n
 
 
+def evaluate_loss_device(model, data, batch_size: int) -> float:
+    """`evaluate_loss` with the sum kept on the device in float64 and read once: the same products in the same order, so the same
+    value, with one synchronisation a pass instead of one a batch."""
+    was_training = model.training
+    model.eval()
+    n = data[0].shape[0]
+    total = torch.zeros((), dtype=torch.float64, device=data[0].device)
+    with torch.no_grad():
+        for i in range(0, n, batch_size):
+            b = tuple(t[i:i + batch_size] for t in data)
+            total += loss(model(b[0]), b)[0].double() * b[0].shape[0]
+    model.train(was_training)
+    return float(total) / n
+
+
+def _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph):
+    """`fit` with `HipAdam`: the same loop, eagerly (graph=False) or with every step a replay of a captured HIP graph (graph=True)."""
+    from .train_graph import HipAdam, graph_refusal
+
+    why = graph_refusal(model)
+    if why is not None:
+        raise ValueError(("graph=True" if graph else 'optimizer="hip"') + f": {why}")
+    val_loss_fn = val_loss_fn or (evaluate_loss_device if graph else evaluate_loss)
+    lr = lr_for_gen(cfg.lr_schedule, gen_n)
+    dev = train[0].device
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(int(seed))
+    n = train[0].shape[0]
+    model.train()
+    path = resolve_heads(model, heads, train[0])
+    opt = HipAdam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
+    try:
+        return _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph)
+    finally:
+        opt.release()   # also when a step, a capture or val_loss_fn raises: the model does not keep gradients a dead table points at
+
+
+def _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph):
+    from .train_graph import GraphedSteps
+
+    graphs = GraphedSteps(model, opt, path, train) if graph else None
+    best_model, best_val, since_best, history = None, math.inf, 0, []
+    for epoch in range(max_epochs):
+        model.train()
+        perm = torch.randperm(n, generator=gen).to(dev)
+        total = graphs.total.zero_() if graph else torch.zeros((), dtype=torch.float64, device=dev)
+        seen = steps = 0
+        for i in range(0, n, batch_size):
+            idx = perm[i:i + batch_size]
+            if idx.shape[0] < 2:
+                continue
+            if graph:
+                graphs.run(idx)
+            else:
+                b = tuple(t[idx] for t in train)
+                opt.zero_grad()
+                step_loss = loss(forward_train(model, b[0], path), b)[0]
+                step_loss.backward()
+                opt.step()
+                total += step_loss.detach().double() * idx.shape[0]
+            seen += idx.shape[0]
+            steps += 1
+        train_loss = float(total) / max(seen, 1)
+        val_loss = float(val_loss_fn(model, val, batch_size))
+        history.append({"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss, "lr": lr, "steps": steps})
+        if val_loss < best_val:
+            best_model, best_val, since_best = copy.deepcopy(model), val_loss, 0
+        else:
+            since_best += 1
+            if since_best >= patience:
+                break
+    if best_model is None:   # no epoch, or no finite val_loss: the model as it is
+        best_model = copy.deepcopy(model)
+    return best_model, best_val, history
+
+
 def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: int = 1337, heads: str = "auto", max_epochs: int = 100,
-        patience: int = 10, val_loss_fn: Optional[Callable] = None):
+        patience: int = 10, val_loss_fn: Optional[Callable] = None, optimizer: str = "auto", graph: bool = False):
     """Train `model` in place on `train`, watching `val` (both tuples (pos, policy, q_penalty, q_no_penalty) of tensors on the
     model's device), as the reference's `trainer.fit` does (training.py:206-225):
 
@@ -106,8 +182,18 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
       consecutive epochs without a strictly lower val_loss (Lightning's EarlyStopping(patience, min_delta=0): a tie is no
       improvement) or after `max_epochs` epochs.  max_epochs = 100 and patience = 10 are the values the reference hard-codes.
 
+    optimizer: "torch" is `torch.optim.Adam`; "hip" is `train_graph.HipAdam`, the same update as one launch with its state and step
+    count on the device; "auto" is "torch" without a graph and "hip" with one.  graph=True (opt-in; an f32 model on a HIP device and
+    optimizer "hip", else ValueError) captures one whole step per batch shape -- the full batch and the epoch's last partial one -- as a
+    HIP graph and replays it (`train_graph.GraphedTrainStep`); the validation pass then sums on the device (`evaluate_loss_device`).
+    History and return values mean the same on every path.
+
     Returns (best_model, best_val_loss, history), history = one dict per epoch: epoch, train_loss (the sample mean of the steps'
     losses), val_loss, lr, steps."""
+    from .train_graph import resolve_optimizer
+
+    if resolve_optimizer(optimizer, graph) == "hip":
+        return _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph)
     val_loss_fn = val_loss_fn or evaluate_loss
     lr = lr_for_gen(cfg.lr_schedule, gen_n)
     opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
@@ -271,11 +357,13 @@ def generation_tensors(games, device=None):
 
 def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_games: int, n_mcts_iterations: int, c_exploration: float,
                      c_ply_penalty: float, self_play_batch_size: int, training_batch_size: int, solver=None, heads: str = "auto", seed: int = 1337,
-                     max_epochs: int = 100, patience: int = 10, timings: Optional[dict] = None, **play_kwargs) -> TrainingGen:
+                     max_epochs: int = 100, patience: int = 10, timings: Optional[dict] = None, optimizer: str = "auto", graph: bool = False,
+                     **play_kwargs) -> TrainingGen:
     """Train a new generation from `parent` (training.py:155-239): self-play with the parent's network, optionally the games'
     `solver_score(solver)`, the reference's train / validation split with mirror images, `fit` on a copy of the parent, and the new
     generation's folder.  solver: a `c4a0_amd.Solver` (None: no scoring).  play_kwargs go to `c4a0_amd.play_games`
-    (resident_games, dirichlet, ...).  timings (a dict) receives the wall seconds of play / split / train."""
+    (resident_games, dirichlet, ...).  timings (a dict) receives the wall seconds of play / split / train.  optimizer and graph are
+    `fit`'s."""
     import time
 
     from . import GameMetadata
@@ -298,7 +386,7 @@ def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_gam
         torch.cuda.synchronize(device)
     t2 = time.perf_counter()
     best_model, best_val, _history = fit(copy.deepcopy(model), train, val, training_batch_size, parent.gen_n + 1, train_config, seed=seed,
-                                         heads=heads, max_epochs=max_epochs, patience=patience)
+                                         heads=heads, max_epochs=max_epochs, patience=patience, optimizer=optimizer, graph=graph)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     t3 = time.perf_counter()

@@ -897,6 +897,45 @@ int c4_train_bn_relu_bwd_bf16(const void* dy_dev, const void* z_dev, const float
                               const float* beta_dev, float eps, uint32_t m, uint32_t n, uint32_t lddy, uint32_t ldz, uint32_t lddz, void* dz_dev,
                               void* dz_t_dev, uint32_t ldt, float* dgamma_dev, float* dbeta_dev, float* db_dev, void* stream);
 
+/* ---- training: the optimiser (c4a0_amd/train_graph.py HipAdam; added functions only: C4_ABI_VERSION stays what it was) -------------
+ * Adam with coupled L2 -- torch.optim.Adam(lr, betas, eps, weight_decay) -- over every parameter of a network in ONE kernel launch,
+ * plus a one-thread launch that advances the step count.  All arrays f32 in device memory.
+ *
+ * The table: n_segs segments in device memory, the table itself 16-byte aligned, built once.  Segment s is n >= 1 elements at p, g
+ * (read only), m and v, each of the four 16-byte aligned, with first_block = sum over the segments before it of
+ * ceil(n / C4_ADAM_BLOCK_ELEMS) (0 for the first); n_blocks is that sum over all segments.  A workgroup's elements belong to one
+ * segment.  Whatever the table says, nothing outside [0, n) of a segment's arrays is read or written.
+ *
+ * The step count: step_dev[0], a uint32 in device memory.  The call computes step t = step_dev[0] + 1 and leaves t behind (t < 2^32),
+ * so a replayed graph advances it and the host never reads it.  From t, in float64 and each rounded to f32 ONCE (PyTorch evaluates
+ * the same expressions in host doubles): bc1 = 1 - beta1^t, bc2 = 1 - beta2^t (the powers by square-and-multiply in f64),
+ *   step_size = f32(lr / bc1),  sqrt_bc2 = f32(sqrt(bc2));  also wd = f32(weight_decay), e = f32(eps), w1 = f32(1 - beta1),
+ *   b2 = f32(beta2), w2 = f32(1 - beta2), the differences taken in f64.
+ * Per element, in f32, these operations in this order (the library is built with -ffp-contract=off; fma(a, b, c) is ONE rounding of
+ * a b + c and appears only where it is written):
+ *   g' = fma(wd, p, g)                     (weight_decay == 0: g' = g, p is not multiplied)
+ *   m' = fma(w1, g' - m, m)                (the lerp form m + (1 - beta1)(g' - m) of torch's lerp_, not beta1 m + (1 - beta1) g')
+ *   v' = fma(w2 * g', g', b2 * v)
+ *   p' = fma(-step_size, m' / (sqrt(v') / sqrt_bc2 + e), p)        (sqrt and both divisions correctly rounded)
+ * and p', m', v' are stored.  tests/adam_ref.py restates this in float64.  Elements are independent and there are no atomics: two
+ * calls from the same state give the same bytes; a NaN or an infinity in g poisons that element's p, m and v and no other.
+ * The call does not synchronise, allocate or copy: it may be captured into a graph.  C4_ERR_BAD_ARG with a c4_last_error_string, and
+ * nothing launched: a null table or step_dev, n_segs == 0, n_blocks == 0, n_blocks < n_segs, a table that is not 16-byte aligned, a
+ * step_dev that is not 4-byte aligned. */
+#define C4_ADAM_BLOCK_ELEMS 4096  /* c4_train_adam_block_elems(): the elements of one workgroup */
+typedef struct c4_adam_segment {
+  float* p;             /* the parameter, updated in place */
+  const float* g;       /* its gradient */
+  float* m;             /* exp_avg, updated in place */
+  float* v;             /* exp_avg_sq, updated in place */
+  uint64_t n;           /* elements */
+  uint32_t first_block; /* the first workgroup of this segment */
+  uint32_t reserved;    /* 0 */
+} c4_adam_segment;      /* 48 bytes */
+int c4_train_adam_f32(const c4_adam_segment* table_dev, uint32_t n_segs, uint32_t n_blocks, uint32_t* step_dev, double lr, double beta1,
+                      double beta2, double eps, double weight_decay, void* stream);
+int c4_train_adam_block_elems(void); /* == C4_ADAM_BLOCK_ELEMS */
+
 /* ---- exact solver ----------------------------------------------------------------------------------------------------------
  * What the reference gets from Pascal Pons' c4solver binary, its opening book and a rocksdb cache (rust/src/solver.rs): here a HIP
  * alpha-beta search with no binary, no book and no database.  These calls only ADD functions: C4_ABI_VERSION stays what it was.

@@ -1,6 +1,6 @@
 """The training kernels of the heads' hidden blocks beside the stock PyTorch ops, on the GPU -> profiles/train_rate.json.
 
-    python tools/train_rate.py [out.json] [--no-generation] [--max-epochs E]
+    python tools/train_rate.py [out.json] [--no-generation] [--max-epochs E] [--bf16 | --graph]
 
 (a) At m = 2 000 rows, F = 1 344 (the default network's heads at the reference's training batch): every kernel of c4_train.hip and
     the forward c4_linear_f32 beside the PyTorch op that does the same job on the same tensors -- F.linear, dz @ W, dz.T @ x (+ the
@@ -15,6 +15,10 @@
     and each of the three c4_linear_bf16 products (forward, dgrad, wgrad) beside the stock op on the same tensors; one hidden block
     forward + backward and the whole optimiser step with heads="bf16", heads="torch" and torch.autocast(bfloat16) on the stock module
     (autocast also runs the tower's convolutions in bf16, which heads="bf16" does not), each callable timed in turn, medians of 7 rounds.
+(e) --graph: training from a captured HIP graph -> profiles/train_rate_graph.json.  c4_train_adam_f32 on the default network's parameters
+    beside torch.optim.Adam.step() on the same parameters, with the bytes a second it reaches against the 28 bytes a parameter it must
+    move; the whole step for heads in {torch, hip, bf16} x {eager torch.optim.Adam (the stock loop), eager HipAdam, graph replay}, all
+    nine callables timed in turn; and the default-shaped generation of (c) with graph=True beside graph=False for each head path.
 Speed is recorded here, never asserted in a test."""
 import ctypes as C
 import json
@@ -231,7 +235,64 @@ def bf16_leg():
     return out
 
 
-def generation(max_epochs: int, heads: str):
+def graph_leg():
+    """c4_train_adam_f32 beside torch.optim.Adam.step(), and the whole step of ModelConfig(1, 32, 4, 2) at batch 2 000 for every head
+    path, eager with torch.optim.Adam, eager with HipAdam and as a graph replay."""
+    from c4a0_amd import training as T
+    from c4a0_amd.nn import ConnectFourNet, ModelConfig
+    from c4a0_amd.train_graph import GraphedTrainStep, HipAdam
+    from c4a0_amd.train_heads import forward_train
+
+    g = torch.Generator().manual_seed(1)
+    cell = torch.randint(0, 3, (M, 6, 7), generator=g)
+    data = (torch.stack([cell == 1, cell == 2], 1).float().to(dev), torch.softmax(torch.randn(M, 7, generator=g), 1).to(dev),
+            (torch.rand(M, generator=g) * 2 - 1).to(dev), (torch.rand(M, generator=g) * 2 - 1).to(dev))
+    idx = torch.randperm(M, generator=g).to(dev)
+
+    def fresh():
+        torch.manual_seed(0)
+        return ConnectFourNet(ModelConfig(1, 32, 4, 2)).to(dev).train()
+
+    # the optimiser alone, on gradients that stay where one backward left them
+    models = {"hip": fresh(), "torch": fresh()}
+    opts = {"hip": HipAdam(models["hip"].parameters(), lr=2e-3, weight_decay=4e-4),
+            "torch": torch.optim.Adam(models["torch"].parameters(), lr=2e-3, weight_decay=4e-4)}
+    for model in models.values():
+        T.loss(model(data[0]), data)[0].backward()
+    n_params = sum(q.numel() for q in models["hip"].parameters())
+    adam = alternating({name: opt.step for name, opt in opts.items()})
+    adam.update(parameters=n_params, tensors=len(opts["hip"].params), bytes_per_parameter=28,
+                hip_bytes_per_s=28.0 * n_params / (adam["hip"]["us"] * 1e-6))
+
+    def step_fn(heads, kind):
+        model = fresh()
+        if kind == "graph":
+            graphed = GraphedTrainStep(model, HipAdam(model.parameters(), lr=2e-3, weight_decay=4e-4), heads, M, data)
+            return lambda: graphed.run(idx)
+        opt = HipAdam(model.parameters(), lr=2e-3, weight_decay=4e-4) if kind == "eager_hip_adam" else \
+            torch.optim.Adam(model.parameters(), lr=2e-3, weight_decay=4e-4)
+
+        def run():
+            b = tuple(t[idx] for t in data)
+            if kind == "eager_hip_adam":
+                opt.zero_grad()
+            else:
+                opt.zero_grad(set_to_none=True)
+            T.loss(forward_train(model, b[0], heads), b)[0].backward()
+            opt.step()
+
+        return run
+
+    fns = {f"{heads}/{kind}": step_fn(heads, kind) for heads in ("torch", "hip", "bf16") for kind in ("eager_torch_adam", "eager_hip_adam", "graph")}
+    step = alternating(fns, launches=5)
+    base = step["torch/eager_torch_adam"]["us"]
+    for v in step.values():
+        v["ms"] = v["us"] * 1e-3
+        v["speedup_over_eager_torch"] = base / v["us"]
+    return {"adam": adam, "step": dict(step, batch=M, model=[1, 32, 4, 2])}
+
+
+def generation(max_epochs: int, heads: str, graph: bool = False):
     from c4a0_amd import training as T
     from c4a0_amd.nn import ModelConfig
 
@@ -239,8 +300,9 @@ def generation(max_epochs: int, heads: str):
         torch.manual_seed(0)
         parent = T.TrainingGen.load_latest_with_default(base, 1400, 6.6, 0.01, 2000, 2000, ModelConfig(1, 32, 4, 2), T.TrainConfig({0: 2e-3}, 4e-4))
         timings = {}
-        gen = T.train_single_gen(base, dev, parent, 1700, 1400, 6.6, 0.01, 2000, 2000, heads=heads, max_epochs=max_epochs, timings=timings)
-        timings.update(heads=heads, max_epochs=max_epochs, val_loss=gen.val_loss, games=1700, n_mcts_iterations=1400, batch=2000)
+        gen = T.train_single_gen(base, dev, parent, 1700, 1400, 6.6, 0.01, 2000, 2000, heads=heads, max_epochs=max_epochs, timings=timings,
+                                 graph=graph)
+        timings.update(heads=heads, graph=graph, max_epochs=max_epochs, val_loss=gen.val_loss, games=1700, n_mcts_iterations=1400, batch=2000)
         return timings
 
 
@@ -252,8 +314,27 @@ def main():
     ap.add_argument("--no-generation", action="store_true")
     ap.add_argument("--max-epochs", type=int, default=10)
     ap.add_argument("--bf16", action="store_true", help='the heads="bf16" leg alone -> profiles/train_rate_bf16.json')
+    ap.add_argument("--graph", action="store_true", help="the graphed-step leg alone -> profiles/train_rate_graph.json")
     a = ap.parse_args()
     out_path, max_epochs = a.out, a.max_epochs
+    if a.graph:
+        if out_path == ap.get_default("out"):
+            out_path = os.path.join(ROOT, "profiles", "train_rate_graph.json")
+        res = {"device": torch.cuda.get_device_name(0)}
+        res.update(graph_leg())
+        print(json.dumps(res, indent=1), flush=True)
+        if not a.no_generation:
+            generation(1, "torch")   # not recorded: the process's first generation pays the libraries' one-time initialisation
+            res["generation"] = []
+            for heads in ("torch", "hip", "bf16"):
+                for graph in (False, True):
+                    res["generation"].append(generation(max_epochs, heads, graph))
+                    print(json.dumps(res["generation"][-1]), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     if a.bf16:
         if out_path == ap.get_default("out"):
             out_path = os.path.join(ROOT, "profiles", "train_rate_bf16.json")
