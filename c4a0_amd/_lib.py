@@ -120,6 +120,7 @@ class AdamSegment(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+TOWER_CHUNK_BOARDS = 16   # include/c4a0_hip.h C4_TRAIN_TOWER_CHUNK_BOARDS: the rows of a training-tower reduction are split by 16 boards
 ADAM_BLOCK_ELEMS = 4096   # include/c4a0_hip.h C4_ADAM_BLOCK_ELEMS == c4_train_adam_block_elems()
 
 SOLVE_FULL_COLUMN, SOLVE_UNSOLVED = -1000, -32768   # include/c4a0_hip.h C4_SOLVE_FULL_COLUMN, C4_SOLVE_UNSOLVED
@@ -204,6 +205,13 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp]),
     "c4_train_linear_dgrad_f32": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "c4_train_linear_wgrad_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "c4_train_tower_work_bytes": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_uint64)]),
+    "c4_train_conv0_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "c4_train_conv3x3_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "c4_train_conv0_wgrad_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "c4_train_conv3x3_wgrad_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "c4_train_bn2d_relu_res_fwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "c4_train_bn2d_relu_res_bwd_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "c4_train_cast_bf16": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     "c4_train_bn_relu_fwd_bf16": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "c4_train_bn_relu_bwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

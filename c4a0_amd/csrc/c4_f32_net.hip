@@ -234,6 +234,12 @@ int launched(const char* what, hipError_t e) {
 
 }  // namespace
 
+// The tower's convolution for c4_train_tower.hip: the same launch as c4_conv_tower_f32's (same tiles, same chain), no activation.
+hipError_t c4f32::launch_train_conv(bool first, const float* x, const float* w, const float* bias, float* y, uint32_t cells, uint32_t cp,
+                                    hipStream_t stream) {
+  return first ? launch_conv<kConv0, kEpiNone>(x, w, bias, y, cells, cp, stream) : launch_conv<kConv, kEpiNone>(x, w, bias, y, cells, cp, stream);
+}
+
 extern "C" int c4_conv_tower_f32(const float* planes_dev, const float* w0_dev, const float* w_dev, const float* bias_dev, uint32_t n_boards,
                                  uint32_t channels, uint32_t n_blocks, float* out_dev, float* work_dev, void* stream) {
   if (!planes_dev || !w0_dev || !bias_dev || !out_dev || (n_blocks && (!w_dev || !work_dev)))

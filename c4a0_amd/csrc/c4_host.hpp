@@ -75,6 +75,15 @@ inline dim3 grid_for(uint64_t n, int bs = 256) { return dim3((unsigned)((n + bs 
 
 }  // namespace c4host
 
+namespace c4f32 {
+
+// One convolution of the f32 tower without activation (c4_f32_net.hip: f32_gemm<kConv0 | kConv, NT, 4, kEpiNone>, the summation order of
+// include/c4a0_hip.h's "f32 evaluator"): first = planes [G][2][6][7] x w0 [cp][32], else x [cells][cp] x w [cp][9 cp]; y [cells][cp].
+hipError_t launch_train_conv(bool first, const float* x, const float* w, const float* bias, float* y, uint32_t cells, uint32_t cp,
+                             hipStream_t stream);
+
+}  // namespace c4f32
+
 // A HIP call inside an entry point: a failure ends the entry point with C4_ERR_HIP and "<the call>: <HIP's message>".
 #define HIP_TRY(expr)                                                                              \
   do {                                                                                             \

@@ -116,7 +116,7 @@ class HipAdam:
 
 class GraphedTrainStep:
     """One optimiser step of `model` on `batch_size` rows of `train` as a HIP graph.  The graph holds the gather of the batch from the
-    training tensors by the static index buffer, `opt.zero_grad()`, `forward_train(model, pos, heads_path)`, `loss`, backward,
+    training tensors by the static index buffer, `opt.zero_grad()`, `forward_train(model, pos, heads_path, tower_path)`, `loss`, backward,
     `opt.step()` and `total += loss * rows` (`total`: a float64 device scalar, the epoch's running sum; one is made if none is given).
     `run(idx)` copies the indices into the static buffer and replays: nothing else happens on the host.
 
@@ -125,7 +125,7 @@ class GraphedTrainStep:
     restored in place after them, and a capture executes nothing: the first replay is the first step."""
 
     def __init__(self, model: nn.Module, opt: HipAdam, heads_path: str, batch_size: int, train: Sequence[torch.Tensor],
-                 total: Optional[torch.Tensor] = None):
+                 total: Optional[torch.Tensor] = None, tower_path: str = "torch"):
         from .session import capture
         from .train_heads import forward_train
         from .training import loss
@@ -136,7 +136,7 @@ class GraphedTrainStep:
         if batch_size < 2:
             raise ValueError("a training step needs at least 2 rows (BatchNorm in train mode)")
         dev = opt.device
-        self.model, self.opt, self.heads_path, self.batch_size = model, opt, heads_path, int(batch_size)
+        self.model, self.opt, self.heads_path, self.tower_path, self.batch_size = model, opt, heads_path, tower_path, int(batch_size)
         self.train = tuple(train)
         self.total = total if total is not None else torch.zeros((), dtype=torch.float64, device=dev)
         self.idx = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)
@@ -147,7 +147,7 @@ class GraphedTrainStep:
             for src, dst in zip(self.train, self.batch):
                 torch.index_select(src, 0, self.idx, out=dst)
             opt.zero_grad()
-            step_loss = loss(forward_train(model, self.pos, heads_path), self.batch)[0]
+            step_loss = loss(forward_train(model, self.pos, heads_path, tower_path), self.batch)[0]
             step_loss.backward()
             opt.step()
             self.total += step_loss.detach().double() * self.batch_size
@@ -179,8 +179,8 @@ class GraphedSteps:
     """The graphs of one `fit`: one `GraphedTrainStep` per batch shape, captured when the shape first comes (two at most: the full
     batch and the epoch's last partial one), all adding to one `total`."""
 
-    def __init__(self, model: nn.Module, opt: HipAdam, heads_path: str, train: Sequence[torch.Tensor]):
-        self.model, self.opt, self.heads_path, self.train = model, opt, heads_path, train
+    def __init__(self, model: nn.Module, opt: HipAdam, heads_path: str, train: Sequence[torch.Tensor], tower_path: str = "torch"):
+        self.model, self.opt, self.heads_path, self.tower_path, self.train = model, opt, heads_path, tower_path, train
         self.total = torch.zeros((), dtype=torch.float64, device=opt.device)
         self.by_rows: Dict[int, GraphedTrainStep] = {}
 
@@ -188,5 +188,5 @@ class GraphedSteps:
         rows = int(idx.shape[0])
         step = self.by_rows.get(rows)
         if step is None:
-            step = self.by_rows[rows] = GraphedTrainStep(self.model, self.opt, self.heads_path, rows, self.train, self.total)
+            step = self.by_rows[rows] = GraphedTrainStep(self.model, self.opt, self.heads_path, rows, self.train, self.total, self.tower_path)
         step.run(idx)

@@ -5,7 +5,7 @@ the default network are over 90 % of a training step's FLOPs.  `HiddenBlockFunct
 `c4_linear_f32` (z = x W^T + b), `c4_train_bn_relu_fwd_f32`, `c4_train_bn_relu_bwd_f32`, `c4_train_linear_dgrad_f32` and
 `c4_train_linear_wgrad_f32` (c4a0_amd/csrc/c4_train.hip); `forward_train` walks the unchanged module tree of `c4a0_amd.nn.ConnectFourNet`
 and sends its hidden triples through it.  The tower, the two output layers, log-softmax, tanh and the loss stay stock PyTorch
-autograd: that is plumbing.
+autograd by default; tower="hip" (opt-in) sends the tower through c4a0_amd/train_tower.py's deterministic kernels instead.
 
 heads="bf16" (opt-in) runs the same triples in bf16 mixed precision: `HiddenBlockBf16Function` rounds x and the f32 master weights to
 bf16, takes all three products of a step -- forward x W^T, dgrad dz W, wgrad dz^T x -- from the bf16 MFMA GEMM `c4_linear_bf16`, and the
@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import check, lib
+from .train_tower import resolve_tower, tower_forward
 
 HEADS = ("auto", "hip", "torch", "bf16")
 
@@ -252,14 +253,23 @@ def _head(seq: nn.Sequential, x: torch.Tensor, path: str = "hip") -> torch.Tenso
     return x
 
 
-def forward_train(model: nn.Module, planes: torch.Tensor, heads: str = "auto") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def forward_train(model: nn.Module, planes: torch.Tensor, heads: str = "auto", tower: str = "torch") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """`model(planes)` -- (policy log-probabilities [B, 7], q_penalty [B], q_no_penalty [B]) -- with autograd, the hidden triples of
     both heads on the HIP kernels where heads resolves to "hip" (an f32 model in train mode on a HIP device whose conv_filter_size is a
-    multiple of 16) or to "bf16" (the same, a multiple of 32; bf16 mixed precision), else the plain module forward."""
+    multiple of 16) or to "bf16" (the same, a multiple of 32; bf16 mixed precision), else the plain module forward.  tower: "torch" (the
+    module's convolutions), "hip" (train_tower.tower_forward: the tower forward and backward on the deterministic f32 kernels; ValueError
+    where they cannot run) or "auto" (train_tower.AUTO_TOWER)."""
     path = resolve_heads(model, heads, planes)
-    if path == "torch":
+    tower_path = resolve_tower(model, tower, planes)
+    if path == "torch" and tower_path == "torch":
         return model(planes)
-    x = model.conv(planes)
-    x = x.reshape(x.shape[0], -1)
+    if tower_path == "hip":
+        x = tower_forward(model.conv, planes)
+    else:
+        x = model.conv(planes)
+        x = x.reshape(x.shape[0], -1)
+    if path == "torch":
+        q = model.fc_value(x)
+        return model.fc_policy(x), q[:, 0], q[:, 1]
     q = _head(model.fc_value, x, path)
     return _head(model.fc_policy, x, path), q[:, 0], q[:, 1]

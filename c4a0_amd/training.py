@@ -23,6 +23,7 @@ import torch
 
 from .nn import ConnectFourNet, ModelConfig
 from .train_heads import forward_train, resolve_heads
+from .train_tower import resolve_tower
 
 EPS = 1e-8  # nn.py:57: avoids log(0)
 
@@ -107,7 +108,7 @@ def evaluate_loss_device(model, data, batch_size: int) -> float:
     return float(total) / n
 
 
-def _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph):
+def _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph, tower="torch"):
     """`fit` with `HipAdam`: the same loop, eagerly (graph=False) or with every step a replay of a captured HIP graph (graph=True)."""
     from .train_graph import HipAdam, graph_refusal
 
@@ -122,17 +123,18 @@ def _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs,
     n = train[0].shape[0]
     model.train()
     path = resolve_heads(model, heads, train[0])
+    tower_path = resolve_tower(model, tower, train[0])
     opt = HipAdam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
     try:
-        return _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph)
+        return _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph, tower_path)
     finally:
         opt.release()   # also when a step, a capture or val_loss_fn raises: the model does not keep gradients a dead table points at
 
 
-def _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph):
+def _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph, tower_path="torch"):
     from .train_graph import GraphedSteps
 
-    graphs = GraphedSteps(model, opt, path, train) if graph else None
+    graphs = GraphedSteps(model, opt, path, train, tower_path) if graph else None
     best_model, best_val, since_best, history = None, math.inf, 0, []
     for epoch in range(max_epochs):
         model.train()
@@ -148,7 +150,7 @@ def _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, m
             else:
                 b = tuple(t[idx] for t in train)
                 opt.zero_grad()
-                step_loss = loss(forward_train(model, b[0], path), b)[0]
+                step_loss = loss(forward_train(model, b[0], path, tower_path), b)[0]
                 step_loss.backward()
                 opt.step()
                 total += step_loss.detach().double() * idx.shape[0]
@@ -169,7 +171,7 @@ def _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, m
 
 
 def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: int = 1337, heads: str = "auto", max_epochs: int = 100,
-        patience: int = 10, val_loss_fn: Optional[Callable] = None, optimizer: str = "auto", graph: bool = False):
+        patience: int = 10, val_loss_fn: Optional[Callable] = None, optimizer: str = "auto", graph: bool = False, tower: str = "auto"):
     """Train `model` in place on `train`, watching `val` (both tuples (pos, policy, q_penalty, q_no_penalty) of tensors on the
     model's device), as the reference's `trainer.fit` does (training.py:206-225):
 
@@ -188,12 +190,16 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
     HIP graph and replays it (`train_graph.GraphedTrainStep`); the validation pass then sums on the device (`evaluate_loss_device`).
     History and return values mean the same on every path.
 
+    tower: `forward_train`'s -- "torch" (the stock convolutions), "hip" (opt-in: the tower forward and backward on the deterministic
+    kernels of `train_tower`; with heads="hip" and optimizer="hip" a fit then repeats itself byte for byte, eagerly and from the graph)
+    or "auto" (`train_tower.AUTO_TOWER`: "torch").
+
     Returns (best_model, best_val_loss, history), history = one dict per epoch: epoch, train_loss (the sample mean of the steps'
     losses), val_loss, lr, steps."""
     from .train_graph import resolve_optimizer
 
     if resolve_optimizer(optimizer, graph) == "hip":
-        return _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph)
+        return _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph, tower)
     val_loss_fn = val_loss_fn or evaluate_loss
     lr = lr_for_gen(cfg.lr_schedule, gen_n)
     opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
@@ -203,6 +209,7 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
     n = train[0].shape[0]
     model.train()
     path = resolve_heads(model, heads, train[0])
+    tower_path = resolve_tower(model, tower, train[0])
     best_model, best_val, since_best, history = None, math.inf, 0, []
     for epoch in range(max_epochs):
         model.train()
@@ -215,7 +222,7 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
                 continue
             b = tuple(t[idx] for t in train)
             opt.zero_grad(set_to_none=True)
-            step_loss = loss(forward_train(model, b[0], path), b)[0]
+            step_loss = loss(forward_train(model, b[0], path, tower_path), b)[0]
             step_loss.backward()
             opt.step()
             total += step_loss.detach().double() * idx.shape[0]
@@ -358,12 +365,12 @@ def generation_tensors(games, device=None):
 def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_games: int, n_mcts_iterations: int, c_exploration: float,
                      c_ply_penalty: float, self_play_batch_size: int, training_batch_size: int, solver=None, heads: str = "auto", seed: int = 1337,
                      max_epochs: int = 100, patience: int = 10, timings: Optional[dict] = None, optimizer: str = "auto", graph: bool = False,
-                     **play_kwargs) -> TrainingGen:
+                     tower: str = "auto", **play_kwargs) -> TrainingGen:
     """Train a new generation from `parent` (training.py:155-239): self-play with the parent's network, optionally the games'
     `solver_score(solver)`, the reference's train / validation split with mirror images, `fit` on a copy of the parent, and the new
     generation's folder.  solver: a `c4a0_amd.Solver` (None: no scoring).  play_kwargs go to `c4a0_amd.play_games`
-    (resident_games, dirichlet, ...).  timings (a dict) receives the wall seconds of play / split / train.  optimizer and graph are
-    `fit`'s."""
+    (resident_games, dirichlet, ...).  timings (a dict) receives the wall seconds of play / split / train.  optimizer, graph and
+    tower are `fit`'s."""
     import time
 
     from . import GameMetadata
@@ -386,7 +393,7 @@ def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_gam
         torch.cuda.synchronize(device)
     t2 = time.perf_counter()
     best_model, best_val, _history = fit(copy.deepcopy(model), train, val, training_batch_size, parent.gen_n + 1, train_config, seed=seed,
-                                         heads=heads, max_epochs=max_epochs, patience=patience, optimizer=optimizer, graph=graph)
+                                         heads=heads, max_epochs=max_epochs, patience=patience, optimizer=optimizer, graph=graph, tower=tower)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     t3 = time.perf_counter()
@@ -406,13 +413,13 @@ def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_gam
 
 def training_loop(base_dir: str, device, n_self_play_games: int, n_mcts_iterations: int, c_exploration: float, c_ply_penalty: float,
                   self_play_batch_size: int, training_batch_size: int, model_config: ModelConfig, max_gens: Optional[int] = None, solver=None,
-                  train_config: Optional[TrainConfig] = None, heads: str = "auto", **kwargs) -> TrainingGen:
+                  train_config: Optional[TrainConfig] = None, heads: str = "auto", tower: str = "auto", **kwargs) -> TrainingGen:
     """Generation after generation (training.py:242-294) from the latest one of base_dir (generation 0 is created where there is
     none, with `model_config` and `train_config`), until gen_n reaches max_gens (None: for ever)."""
     gen = TrainingGen.load_latest_with_default(base_dir, n_mcts_iterations, c_exploration, c_ply_penalty, self_play_batch_size,
                                                training_batch_size, model_config, train_config)
     while True:
         gen = train_single_gen(base_dir, device, gen, n_self_play_games, n_mcts_iterations, c_exploration, c_ply_penalty, self_play_batch_size,
-                               training_batch_size, solver=solver, heads=heads, **kwargs)
+                               training_batch_size, solver=solver, heads=heads, tower=tower, **kwargs)
         if max_gens is not None and gen.gen_n >= max_gens:
             return gen

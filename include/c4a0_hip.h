@@ -850,6 +850,61 @@ int c4_train_linear_dgrad_f32(const float* dz_dev, const float* w_dev, float* dx
 int c4_train_linear_wgrad_f32(const float* dz_dev, const float* x_dev, float* dw_dev, float* db_dev, uint32_t m, uint32_t n, uint32_t k,
                               uint32_t ldz, uint32_t ldx, void* stream);
 
+/* ---- training the convolution tower (c4a0_amd/train_tower.py tower="hip"; added functions only: C4_ABI_VERSION stays what it was) ------
+ * The tower in train mode (nn.py:64-70, 184-195): Conv2d(2, C), then per block Conv2d(C, C) -> Conv2d(C, C) -> BatchNorm2d with batch
+ * statistics -> ReLU, added to the block's input.  All f32.  Activations and their gradients are cell-major [n_boards][42][C] -- a
+ * row-major matrix [42 n_boards][C], dense -- which is what c4_conv_tower_f32 writes; BatchNorm2d is then a batch norm over the
+ * m = 42 n_boards rows.  channels = C is 16, 32, 48 or 64, n_boards >= 1, 42 n_boards C < 2^31, arrays 16-byte aligned (else
+ * C4_ERR_BAD_ARG, nothing is launched).  Weights are packed as pack_f32_weights packs them: w0 [C][32] with k = 2 tap + ci (zero from 18
+ * on), w [C][9 C] with k = tap C + ci, tap = 3 (dr + 1) + (dc + 1).  No call allocates, copies or synchronises: each may be captured.
+ * work_dev is the caller's, c4_train_tower_work_bytes(n_boards, channels) bytes, its contents meaningless between calls.
+ *
+ * The contract: every output is a fixed function of the inputs.  Each sum has ONE order, decided by (n_boards, C) alone -- never by the
+ * device, its CU count, the launch or an environment variable -- and nothing is added with atomics: two calls give the same bytes.
+ *   chunks     The rows are split into chunks of C4_TRAIN_TOWER_CHUNK_BOARDS = 16 whole boards (672 rows); the last chunk holds what is
+ *              left.  n_chunks = ceil(n_boards / 16).
+ *   forward    c4_train_conv0_f32 / c4_train_conv3x3_f32: z = chain + bias, the "f32 evaluator" chain above (conv0 / conv, act = none).
+ *              c4_train_conv0_f32's bytes are c4_conv_tower_f32(n_blocks = 0)'s.
+ *   dgrad      da[cell][ci] = sum_tap sum_co dz[cell - offset(tap)][co] W[co][tap][ci] is c4_train_conv3x3_f32 on dz with
+ *              W'[ci][(8 - tap) C + co] = W[co][tap C + ci] and a zero bias: the same chain over k' = (8 - tap) C + co.
+ *   wgrad      per chunk, dW_c[co][k] is ONE f32 fmaf chain from +0 over the chunk's rows in ascending order,
+ *              acc = fmaf(X[row][k], dz[row][co], acc), X the im2col row the forward reads (0 off the board, 0 for conv0's k >= 18); rows
+ *              past the batch and cells off the board enter as SELECTED zeros (+0 products of 0 x 0, never 0 x a value read).  db_c[co]:
+ *              four sums s_h from +0 over the chunk's rows = h (mod 4) in ascending order, then (s_0 + s_1) + (s_2 + s_3).
+ *              Then, per element of dW and db: group g = 0..7 adds the chunks g, g + 8, g + 16, .. in order, starting FROM its first chunk;
+ *              the result is ((G_0 + G_1) + ..) + G_{min(8, n_chunks) - 1}.
+ *   batch norm a reduction over rows [r0, r1) in a workgroup of RG = floor(256 / (C / 4)) row groups: group g starts from +0 and adds its
+ *              rows r0 + g, r0 + g + RG, .. in ascending order, then the RG sums are added as a tree: for half = 32, 16, 8, 4, 2, 1,
+ *              G_g += G_{g + half} for every g < half with g + half < RG; the result is G_0.  A column's total
+ *              is that reduction over the chunk's rows, per chunk, and then THE SAME reduction over the n_chunks partial sums.
+ *              Elementwise arithmetic is c4_train_bn_relu_*_f32's, operation for operation (separate multiplies and adds, no fma). */
+#define C4_TRAIN_TOWER_CHUNK_BOARDS 16
+/* *bytes_out = the bytes of work space any call below needs at (n_boards, channels): n_chunks (9 C^2 + C) floats. */
+int c4_train_tower_work_bytes(uint32_t n_boards, uint32_t channels, uint64_t* bytes_out);
+/* z [42 n_boards][C] = conv0(planes [n_boards][2][6][7]) + bias, no activation. */
+int c4_train_conv0_f32(const float* planes_dev, const float* w0_dev, const float* bias_dev, float* z_dev, uint32_t n_boards, uint32_t channels,
+                       void* stream);
+/* z [42 n_boards][C] = conv3x3(x [42 n_boards][C]) + bias, no activation; z must not be x. */
+int c4_train_conv3x3_f32(const float* x_dev, const float* w_dev, const float* bias_dev, float* z_dev, uint32_t n_boards, uint32_t channels,
+                         void* stream);
+/* dw0 [C][32] (columns 18..31 are +0) and db [C] of the first convolution from dz [42 n_boards][C] and the planes.  Two launches. */
+int c4_train_conv0_wgrad_f32(const float* dz_dev, const float* planes_dev, float* dw0_dev, float* db_dev, uint32_t n_boards, uint32_t channels,
+                             float* work_dev, void* stream);
+/* dw [C][9 C] and db [C] of a 3x3 convolution from dz and its input x, both [42 n_boards][C].  Two launches. */
+int c4_train_conv3x3_wgrad_f32(const float* dz_dev, const float* x_dev, float* dw_dev, float* db_dev, uint32_t n_boards, uint32_t channels,
+                               float* work_dev, void* stream);
+/* mean[c], var[c]: the batch mean and the BIASED batch variance (sum (z - mean)^2 / m, two passes) of column c of z over the m = 42 n_boards
+ * rows; y = a + relu(((z - mean) * rstd) * gamma + beta), rstd = 1 / sqrt(var + eps), relu(p) = !(p <= 0) ? p : 0 (a NaN passes); a is the
+ * residual block's input.  z, a, y [m][C].  Three launches. */
+int c4_train_bn2d_relu_res_fwd_f32(const float* z_dev, const float* a_dev, const float* gamma_dev, const float* beta_dev, float eps,
+                                   uint32_t n_boards, uint32_t channels, float* y_dev, float* mean_dev, float* var_dev, float* work_dev,
+                                   void* stream);
+/* The backward of the call above with respect to z, gamma and beta (the gradient with respect to a is dy itself) from dy [m][C] and the z,
+ * mean and var it was given / wrote; the formulas are c4_train_bn_relu_bwd_f32's, corrected deviations included.  Three launches. */
+int c4_train_bn2d_relu_res_bwd_f32(const float* dy_dev, const float* z_dev, const float* mean_dev, const float* var_dev, const float* gamma_dev,
+                                   const float* beta_dev, float eps, uint32_t n_boards, uint32_t channels, float* dz_dev, float* dgamma_dev,
+                                   float* dbeta_dev, float* work_dev, void* stream);
+
 /* ---- bf16 mixed-precision training of the hidden blocks (c4a0_amd/train_heads.py heads="bf16"; added functions only: C4_ABI_VERSION
  * stays what it was): where a block rounds.  Parameters, optimiser state and running statistics stay f32.  Every rounding to bf16 is
  * round to nearest, ties to even (v_cvt_pk_bf16_f32); a value is rounded at the points below and nowhere else; all accumulation is

@@ -1,6 +1,6 @@
 """The training kernels of the heads' hidden blocks beside the stock PyTorch ops, on the GPU -> profiles/train_rate.json.
 
-    python tools/train_rate.py [out.json] [--no-generation] [--max-epochs E] [--bf16 | --graph]
+    python tools/train_rate.py [out.json] [--no-generation] [--max-epochs E] [--bf16 | --graph | --tower]
 
 (a) At m = 2 000 rows, F = 1 344 (the default network's heads at the reference's training batch): every kernel of c4_train.hip and
     the forward c4_linear_f32 beside the PyTorch op that does the same job on the same tensors -- F.linear, dz @ W, dz.T @ x (+ the
@@ -19,6 +19,10 @@
     beside torch.optim.Adam.step() on the same parameters, with the bytes a second it reaches against the 28 bytes a parameter it must
     move; the whole step for heads in {torch, hip, bf16} x {eager torch.optim.Adam (the stock loop), eager HipAdam, graph replay}, all
     nine callables timed in turn; and the default-shaped generation of (c) with graph=True beside graph=False for each head path.
+(f) --tower: the opt-in tower="hip" path -> profiles/train_rate_tower.json.  At ModelConfig(1, 32, 4, 2), batch 2 000 (84 000 rows of 32
+    channels): each call of c4_train_tower.hip beside the stock op it replaces on the same values (the stock side in its own NCHW layout);
+    the tower's forward + backward alone, stock against train_tower.tower_forward; and the whole step for heads in {torch, bf16} x
+    tower in {torch, hip}, eager with HipAdam and as a graph replay, beside the stock loop (torch.optim.Adam), all timed in turn.
 Speed is recorded here, never asserted in a test."""
 import ctypes as C
 import json
@@ -292,6 +296,114 @@ def graph_leg():
     return {"adam": adam, "step": dict(step, batch=M, model=[1, 32, 4, 2])}
 
 
+def tower_leg():
+    from c4a0_amd import train_tower as TT
+    from c4a0_amd import training as T
+    from c4a0_amd.nn import ConnectFourNet, ModelConfig
+    from c4a0_amd.train_graph import GraphedTrainStep, HipAdam
+    from c4a0_amd.train_heads import forward_train
+
+    L, ck = _lib.lib(), _lib.check
+    g = torch.Generator().manual_seed(0)
+    b, c = M, 32
+    m = 42 * b
+    cell = torch.randint(0, 3, (b, 6, 7), generator=g)
+    planes = torch.stack([cell == 1, cell == 2], 1).float().to(dev)
+    w0_t, w_t = (torch.randn(c, 2, 3, 3, generator=g) / 18 ** 0.5).to(dev), (torch.randn(c, c, 3, 3, generator=g) / (9 * c) ** 0.5).to(dev)
+    bias, gamma, beta = torch.randn(c, generator=g).to(dev), (torch.rand(c, generator=g) + 0.5).to(dev), torch.randn(c, generator=g).to(dev)
+    zero = torch.zeros(c, device=dev)
+    x, dz, dy, a = (torch.randn(m, c, generator=g).to(dev) for _ in range(4))            # cell-major [42 B][C]
+    nchw = lambda t: t.reshape(b, 6, 7, c).permute(0, 3, 1, 2).contiguous()
+    x_n, dz_n, dy_n, a_n = nchw(x), nchw(dz), nchw(dy), nchw(a)
+    w0, w, wd = TT.pack_conv0(w0_t), TT.pack_conv3x3(w_t), TT.pack_conv3x3_dgrad(w_t)
+    z, y, dx = (torch.empty((m, c), device=dev) for _ in range(3))
+    dw, dw0 = torch.empty((c, 9 * c), device=dev), torch.empty((c, 32), device=dev)
+    mean, var, db, dgamma, dbeta = (torch.empty(c, device=dev) for _ in range(5))
+    work = torch.empty(TT.work_bytes(b, c) // 4, device=dev)
+    ck(L.c4_train_conv3x3_f32(p(x), p(w), p(bias), p(z), b, c, stream()))
+    ck(L.c4_train_bn2d_relu_res_fwd_f32(p(z), p(a), p(gamma), p(beta), EPS, b, c, p(y), p(mean), p(var), p(work), stream()))
+    z_n = nchw(z)
+    zt, gt, bt = z_n.clone().requires_grad_(), gamma.clone().requires_grad_(), beta.clone().requires_grad_()
+    yt = a_n + torch.relu(F.batch_norm(zt, None, None, gt, bt, True, 0.1, EPS))
+    grad = torch.nn.grad
+    kernels = {
+        "conv0_fwd": {"hip": lambda: ck(L.c4_train_conv0_f32(p(planes), p(w0), p(bias), p(z), b, c, stream())),
+                      "torch": lambda: F.conv2d(planes, w0_t, bias, padding=1)},
+        "conv3x3_fwd": {"hip": lambda: ck(L.c4_train_conv3x3_f32(p(x), p(w), p(bias), p(y), b, c, stream())),
+                        "torch": lambda: F.conv2d(x_n, w_t, bias, padding=1)},
+        "conv3x3_dgrad": {"hip": lambda: ck(L.c4_train_conv3x3_f32(p(dz), p(wd), p(zero), p(dx), b, c, stream())),
+                          "torch": lambda: grad.conv2d_input(x_n.shape, w_t, dz_n, padding=1)},
+        "conv3x3_wgrad": {"hip": lambda: ck(L.c4_train_conv3x3_wgrad_f32(p(dz), p(x), p(dw), p(db), b, c, p(work), stream())),
+                          "torch": lambda: (grad.conv2d_weight(x_n, w_t.shape, dz_n, padding=1), dz_n.sum((0, 2, 3)))},
+        "conv0_wgrad": {"hip": lambda: ck(L.c4_train_conv0_wgrad_f32(p(dz), p(planes), p(dw0), p(db), b, c, p(work), stream())),
+                        "torch": lambda: (grad.conv2d_weight(planes, w0_t.shape, dz_n, padding=1), dz_n.sum((0, 2, 3)))},
+        "bn2d_relu_res_fwd": {"hip": lambda: ck(L.c4_train_bn2d_relu_res_fwd_f32(p(z), p(a), p(gamma), p(beta), EPS, b, c, p(y), p(mean), p(var), p(work),
+                                                                                 stream())),
+                              "torch": lambda: a_n + torch.relu(F.batch_norm(z_n, None, None, gamma, beta, True, 0.1, EPS))},
+        "bn2d_relu_res_bwd": {"hip": lambda: ck(L.c4_train_bn2d_relu_res_bwd_f32(p(dy), p(z), p(mean), p(var), p(gamma), p(beta), EPS, b, c, p(dx),
+                                                                                 p(dgamma), p(dbeta), p(work), stream())),
+                              "torch": lambda: torch.autograd.grad(yt, (zt, gt, bt), dy_n, retain_graph=True)},
+    }
+    out = {"shape": {"batch": b, "channels": c, "rows": m, "chunk_boards": _lib.TOWER_CHUNK_BOARDS}, "kernels": {k: alternating(v) for k, v in kernels.items()}}
+    flops = {"conv0_fwd": 2.0 * m * c * 18, "conv0_wgrad": 2.0 * m * c * 18, "conv3x3_fwd": 2.0 * m * c * 9 * c, "conv3x3_dgrad": 2.0 * m * c * 9 * c,
+             "conv3x3_wgrad": 2.0 * m * c * 9 * c}
+    for name, flop in flops.items():
+        for side in out["kernels"][name].values():
+            side["tflops"] = flop / side["us"] * 1e-6
+
+    def fresh():
+        torch.manual_seed(0)
+        return ConnectFourNet(ModelConfig(1, 32, 4, 2)).to(dev).train()
+
+    # the tower alone, forward + backward from a given gradient of its features
+    dfeat = torch.randn(b, 42 * c, generator=g).to(dev)
+
+    def tower_fn(kind):
+        model = fresh()
+
+        def run():
+            model.conv.zero_grad(set_to_none=True)
+            feat = TT.tower_forward(model.conv, planes) if kind == "hip" else model.conv(planes).reshape(b, -1)
+            feat.backward(dfeat)
+
+        return run
+
+    out["tower_fwd_bwd"] = alternating({kind: tower_fn(kind) for kind in ("hip", "torch")}, launches=10)
+    data = (planes, torch.softmax(torch.randn(b, 7, generator=g), 1).to(dev), (torch.rand(b, generator=g) * 2 - 1).to(dev),
+            (torch.rand(b, generator=g) * 2 - 1).to(dev))
+    idx = torch.randperm(b, generator=g).to(dev)
+
+    def step_fn(heads, tower, kind):
+        model = fresh()
+        if kind == "graph":
+            graphed = GraphedTrainStep(model, HipAdam(model.parameters(), lr=2e-3, weight_decay=4e-4), heads, b, data, tower_path=tower)
+            return lambda: graphed.run(idx)
+        opt = HipAdam(model.parameters(), lr=2e-3, weight_decay=4e-4) if kind == "eager_hip_adam" else \
+            torch.optim.Adam(model.parameters(), lr=2e-3, weight_decay=4e-4)
+
+        def run():
+            bt_ = tuple(t[idx] for t in data)
+            if kind == "eager_hip_adam":
+                opt.zero_grad()
+            else:
+                opt.zero_grad(set_to_none=True)
+            T.loss(forward_train(model, bt_[0], heads, tower), bt_)[0].backward()
+            opt.step()
+
+        return run
+
+    fns = {"heads=torch/tower=torch/eager_torch_adam": step_fn("torch", "torch", "eager_torch_adam")}
+    for heads in ("torch", "bf16"):
+        for tower in ("torch", "hip"):
+            for kind in ("eager_hip_adam", "graph"):
+                fns[f"heads={heads}/tower={tower}/{kind}"] = step_fn(heads, tower, kind)
+    step = alternating(fns, launches=5)
+    for v in step.values():
+        v["ms"] = v["us"] * 1e-3
+    out["step"] = dict(step, batch=b, model=[1, 32, 4, 2])
+    return out
+
+
 def generation(max_epochs: int, heads: str, graph: bool = False):
     from c4a0_amd import training as T
     from c4a0_amd.nn import ModelConfig
@@ -315,8 +427,20 @@ def main():
     ap.add_argument("--max-epochs", type=int, default=10)
     ap.add_argument("--bf16", action="store_true", help='the heads="bf16" leg alone -> profiles/train_rate_bf16.json')
     ap.add_argument("--graph", action="store_true", help="the graphed-step leg alone -> profiles/train_rate_graph.json")
+    ap.add_argument("--tower", action="store_true", help='the tower="hip" leg alone -> profiles/train_rate_tower.json')
     a = ap.parse_args()
     out_path, max_epochs = a.out, a.max_epochs
+    if a.tower:
+        if out_path == ap.get_default("out"):
+            out_path = os.path.join(ROOT, "profiles", "train_rate_tower.json")
+        res = {"device": torch.cuda.get_device_name(0)}
+        res.update(tower_leg())
+        print(json.dumps(res, indent=1), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     if a.graph:
         if out_path == ap.get_default("out"):
             out_path = os.path.join(ROOT, "profiles", "train_rate_graph.json")
