@@ -225,12 +225,8 @@ __global__ __launch_bounds__(64) void f32_head_out(const float* __restrict__ hp,
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int launched(const char* what, hipError_t e) {
-  if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-  return C4_OK;
-}
+using c4host::aligned16;
+using c4host::launched;
 
 }  // namespace
 

@@ -73,6 +73,14 @@ void with_flag(bool flag, F&& f) {
 // one thread per element
 inline dim3 grid_for(uint64_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
+// what the entry points of the f32 and training kernels check of their arguments, and how they report a failed launch
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool below_2_31(uint64_t rows, uint64_t ld) { return rows * ld < (1ull << 31); }
+inline int launched(const char* what, hipError_t e) {
+  if (e != hipSuccess) return fail(C4_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+  return C4_OK;
+}
+
 }  // namespace c4host
 
 namespace c4f32 {

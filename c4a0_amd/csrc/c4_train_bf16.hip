@@ -327,14 +327,9 @@ __global__ __launch_bounds__(kThreads) void train_bn_bwd_bf16(const uint16_t* __
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int launched(const char* what, hipError_t e) {
-  if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-  return C4_OK;
-}
-
-bool below_2_31(uint64_t rows, uint64_t ld) { return rows * ld < (1ull << 31); }
+using c4host::aligned16;
+using c4host::below_2_31;
+using c4host::launched;
 
 uint32_t padded(uint32_t m) { return 64 * ((m + 63) / 64); }
 

@@ -304,12 +304,8 @@ __global__ __launch_bounds__(256) void bn2d_bwd_apply(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int launched(const char* what, hipError_t e) {
-  if (e != hipSuccess) return c4host::fail(C4_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-  return C4_OK;
-}
+using c4host::aligned16;
+using c4host::launched;
 
 bool channels_ok(uint32_t c) { return c >= 16 && c <= 64 && c % 16 == 0; }
 

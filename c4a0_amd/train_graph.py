@@ -1,6 +1,7 @@
 """The optimiser step of training as device work only: `HipAdam`, Adam over every parameter of a network in one launch
-(`c4_train_adam_f32`, c4a0_amd/csrc/c4_train_adam.hip), and `GraphedTrainStep`, one whole step -- the gather of the batch, zero_grad,
-`forward_train`, `loss`, backward, the Adam launch and the epoch's running loss -- captured once as a HIP graph and replayed.
+(`c4_train_adam_f32`, c4a0_amd/csrc/c4_train_adam.hip), `train_step`, the one place a step is written down (zero_grad, forward, `loss`,
+backward, the optimiser), and the two ways `fit` runs it: `EagerSteps`, and `GraphedSteps` / `GraphedTrainStep`, one whole step -- the
+gather of the batch, `train_step` and the epoch's running loss -- captured once as a HIP graph and replayed.
 
 An eager step of the default network is bound by the host (2.91 ms a step around 0.6 ms of hidden-block kernels);
 `torch.optim.Adam` alone makes a dozen passes over some 30 tensors and keeps its step count on the host, where a replayed graph cannot
@@ -17,6 +18,10 @@ import torch
 import torch.nn as nn
 
 from ._lib import ADAM_BLOCK_ELEMS, AdamSegment, check, lib
+from .session import capture
+from .train_common import cuda_stream, kernel_refusal, loss
+from .train_heads import forward_resolved, resolve_heads
+from .train_tower import resolve_tower
 
 OPTIMIZERS = ("auto", "torch", "hip")
 WARMUP_STEPS = 3   # eager steps of a shape before its capture: hipBLASLt's workspaces and MIOpen's choice of algorithm are made lazily
@@ -37,15 +42,7 @@ def resolve_optimizer(optimizer: str = "auto", graph: bool = False) -> str:
 
 def graph_refusal(model: nn.Module) -> Optional[str]:
     """Why a step of `model` cannot be captured (or run with HipAdam), or None if it can."""
-    params = list(model.parameters())
-    if not params:
-        return "the model has no parameters"
-    p = params[0]
-    if p.device.type != "cuda":
-        return f"the model is on {p.device}, not on a HIP device"
-    if any(q.dtype != torch.float32 for q in params):
-        return "the model is not f32 (HipAdam's kernel is f32)"
-    return None
+    return kernel_refusal(model, not_f32="the model is not f32 (HipAdam's kernel is f32)")
 
 
 def adam_table(segments: Sequence[Tuple[int, int, int, int, int]]) -> Tuple[np.ndarray, int]:
@@ -91,7 +88,7 @@ class HipAdam:
 
     def step(self) -> None:
         check(lib().c4_train_adam_f32(self.table.data_ptr(), self.n_segs, self.n_blocks, self.step_count.data_ptr(), self.lr, self.betas[0],
-                                      self.betas[1], self.eps, self.weight_decay, torch.cuda.current_stream(self.device).cuda_stream))
+                                      self.betas[1], self.eps, self.weight_decay, cuda_stream(self.device)))
 
     def zero_grad(self) -> None:
         for p, g in zip(self.params, self.grads):
@@ -114,10 +111,40 @@ class HipAdam:
             p.grad = None
 
 
+def train_step(model: nn.Module, opt, batch: Sequence[torch.Tensor], heads_path: str, tower_path: str) -> torch.Tensor:
+    """THE optimiser step of training on `batch` = (pos, policy, q_penalty, q_no_penalty), on resolved paths: zero_grad, forward, `loss`,
+    backward, `opt.step()`.  Returns the step's loss, detached.  `torch.optim.Adam` drops its gradients; `HipAdam.zero_grad()` zeroes
+    its persistent ones in place."""
+    if isinstance(opt, torch.optim.Optimizer):
+        opt.zero_grad(set_to_none=True)
+    else:
+        opt.zero_grad()
+    step_loss = loss(forward_resolved(model, batch[0], heads_path, tower_path), batch)[0]
+    step_loss.backward()
+    opt.step()
+    return step_loss.detach()
+
+
+class EagerSteps:
+    """The steps of one `fit` run eagerly, with either optimiser: `run(idx)` gathers the batch and takes `train_step`; `total` (a float64
+    device scalar, a fresh zero after every `reset()`) is the epoch's running sum of loss * rows."""
+
+    def __init__(self, model: nn.Module, opt, heads_path: str, train: Sequence[torch.Tensor], tower_path: str):
+        self.model, self.opt, self.heads_path, self.tower_path, self.train = model, opt, heads_path, tower_path, train
+        self.reset()
+
+    def reset(self) -> None:
+        self.total = torch.zeros((), dtype=torch.float64, device=self.train[0].device)
+
+    def run(self, idx: torch.Tensor) -> None:
+        step_loss = train_step(self.model, self.opt, tuple(t[idx] for t in self.train), self.heads_path, self.tower_path)
+        self.total += step_loss.double() * idx.shape[0]
+
+
 class GraphedTrainStep:
     """One optimiser step of `model` on `batch_size` rows of `train` as a HIP graph.  The graph holds the gather of the batch from the
-    training tensors by the static index buffer, `opt.zero_grad()`, `forward_train(model, pos, heads_path, tower_path)`, `loss`, backward,
-    `opt.step()` and `total += loss * rows` (`total`: a float64 device scalar, the epoch's running sum; one is made if none is given).
+    training tensors by the static index buffer, `train_step` on heads_path and tower_path (checked once, here, as `forward_train` checks
+    them) and `total += loss * rows` (`total`: a float64 device scalar, the epoch's running sum; one is made if none is given).
     `run(idx)` copies the indices into the static buffer and replays: nothing else happens on the host.
 
     Before the capture WARMUP_STEPS eager steps run on the capture's side stream, because the vendor libraries initialise lazily; the
@@ -126,18 +153,15 @@ class GraphedTrainStep:
 
     def __init__(self, model: nn.Module, opt: HipAdam, heads_path: str, batch_size: int, train: Sequence[torch.Tensor],
                  total: Optional[torch.Tensor] = None, tower_path: str = "torch"):
-        from .session import capture
-        from .train_heads import forward_train
-        from .training import loss
-
         why = graph_refusal(model)
         if why is not None:
             raise ValueError(f"graph=True: {why}")
         if batch_size < 2:
             raise ValueError("a training step needs at least 2 rows (BatchNorm in train mode)")
         dev = opt.device
-        self.model, self.opt, self.heads_path, self.tower_path, self.batch_size = model, opt, heads_path, tower_path, int(batch_size)
         self.train = tuple(train)
+        heads_path, tower_path = resolve_heads(model, heads_path, self.train[0]), resolve_tower(model, tower_path, self.train[0])
+        self.model, self.opt, self.heads_path, self.tower_path, self.batch_size = model, opt, heads_path, tower_path, int(batch_size)
         self.total = total if total is not None else torch.zeros((), dtype=torch.float64, device=dev)
         self.idx = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)
         self.batch = tuple(torch.empty((self.batch_size,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in self.train)
@@ -146,11 +170,7 @@ class GraphedTrainStep:
         def step():
             for src, dst in zip(self.train, self.batch):
                 torch.index_select(src, 0, self.idx, out=dst)
-            opt.zero_grad()
-            step_loss = loss(forward_train(model, self.pos, heads_path, tower_path), self.batch)[0]
-            step_loss.backward()
-            opt.step()
-            self.total += step_loss.detach().double() * self.batch_size
+            self.total += train_step(model, opt, self.batch, heads_path, tower_path).double() * self.batch_size
 
         keep = [t for t in list(model.parameters()) + list(model.buffers()) + opt.state() + [self.total]]
         current = torch.cuda.current_stream(dev)
@@ -183,6 +203,9 @@ class GraphedSteps:
         self.model, self.opt, self.heads_path, self.tower_path, self.train = model, opt, heads_path, tower_path, train
         self.total = torch.zeros((), dtype=torch.float64, device=opt.device)
         self.by_rows: Dict[int, GraphedTrainStep] = {}
+
+    def reset(self) -> None:
+        self.total.zero_()   # in place: the captured steps add to this tensor
 
     def run(self, idx: torch.Tensor) -> None:
         rows = int(idx.shape[0])

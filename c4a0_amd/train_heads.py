@@ -20,13 +20,10 @@ import torch
 import torch.nn as nn
 
 from ._lib import check, lib
+from .train_common import cuda_stream, kernel_refusal, update_running_stats
 from .train_tower import resolve_tower, tower_forward
 
 HEADS = ("auto", "hip", "torch", "bf16")
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _rows(t: torch.Tensor) -> torch.Tensor:
@@ -52,7 +49,7 @@ class HiddenBlockFunction(torch.autograd.Function):
         y = torch.empty((m, n), dtype=torch.float32, device=dev)
         mean = torch.empty(n, dtype=torch.float32, device=dev)
         var = torch.empty(n, dtype=torch.float32, device=dev)
-        s = _stream(dev)
+        s = cuda_stream(dev)
         check(L.c4_linear_f32(x.data_ptr(), w.data_ptr(), bias.data_ptr(), z.data_ptr(), m, n, k, x.stride(0), n, 0, s))
         check(L.c4_train_bn_relu_fwd_f32(z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, m, n, n, n, y.data_ptr(), mean.data_ptr(),
                                          var.data_ptr(), s))
@@ -70,7 +67,7 @@ class HiddenBlockFunction(torch.autograd.Function):
         dz = torch.empty((m, n), dtype=torch.float32, device=dev)
         dgamma = torch.empty(n, dtype=torch.float32, device=dev)
         dbeta = torch.empty(n, dtype=torch.float32, device=dev)
-        s = _stream(dev)
+        s = cuda_stream(dev)
         check(L.c4_train_bn_relu_bwd_f32(dy.data_ptr(), z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ctx.eps,
                                          m, n, dy.stride(0), n, n, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), s))
         dx = None
@@ -98,14 +95,14 @@ def _cast_bf16(src: torch.Tensor, dst: bool, dst_t: bool):
     out = torch.empty((m, c), dtype=torch.bfloat16, device=src.device) if dst else None
     out_t = torch.empty((c, mp), dtype=torch.bfloat16, device=src.device) if dst_t else None
     check(lib().c4_train_cast_bf16(src.data_ptr(), int(src.dtype == torch.bfloat16), m, c, src.stride(0), out.data_ptr() if dst else None, c,
-                                   out_t.data_ptr() if dst_t else None, mp, _stream(src.device)))
+                                   out_t.data_ptr() if dst_t else None, mp, cuda_stream(src.device)))
     return out, out_t
 
 
 def _linear_bf16(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, m: int, n: int, k: int) -> torch.Tensor:
     """bf16(x[:m, :k] w[:n, :k]^T + bias) [m][n] by c4_linear_bf16, the tile configuration automatic"""
     y = torch.empty((m, n), dtype=torch.bfloat16, device=x.device)
-    check(lib().c4_linear_bf16(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), m, n, k, x.stride(0), n, 0, 0, _stream(x.device)))
+    check(lib().c4_linear_bf16(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), m, n, k, x.stride(0), n, 0, 0, cuda_stream(x.device)))
     return y
 
 
@@ -139,7 +136,7 @@ class HiddenBlockBf16Function(torch.autograd.Function):
         mean = torch.empty(n, dtype=torch.float32, device=dev)
         var = torch.empty(n, dtype=torch.float32, device=dev)
         check(L.c4_train_bn_relu_fwd_bf16(z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, m, n, n, n, y.data_ptr(), mean.data_ptr(),
-                                          var.data_ptr(), y_t.data_ptr() if emit_t else None, mp, _stream(dev)))
+                                          var.data_ptr(), y_t.data_ptr() if emit_t else None, mp, cuda_stream(dev)))
         ctx.save_for_backward(xb, xb_t, wb, z, mean, var, gamma, beta)
         ctx.eps = eps
         if emit_t:
@@ -162,7 +159,7 @@ class HiddenBlockBf16Function(torch.autograd.Function):
         db = torch.empty(n, dtype=torch.float32, device=dev)
         check(L.c4_train_bn_relu_bwd_bf16(dy.data_ptr(), z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ctx.eps,
                                           m, n, dy.stride(0), n, n, dz.data_ptr(), dz_t.data_ptr(), mp, dgamma.data_ptr(), dbeta.data_ptr(),
-                                          db.data_ptr(), _stream(dev)))
+                                          db.data_ptr(), cuda_stream(dev)))
         zeros = torch.zeros(max(n, k), dtype=torch.float32, device=dev)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -192,33 +189,21 @@ def hidden_block(block: nn.Sequential, x: torch.Tensor, path: str = "hip", emit_
             y.c4_transposed = y_t
     else:
         y, mean, var = HiddenBlockFunction.apply(x, lin.weight, lin.bias, bn.weight, bn.bias, bn.eps)
-    if bn.track_running_stats and bn.running_mean is not None:
-        m = x.shape[0]
-        with torch.no_grad():
-            bn.num_batches_tracked += 1
-            f = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            bn.running_mean.mul_(1.0 - f).add_(mean, alpha=f)
-            bn.running_var.mul_(1.0 - f).add_(var * (m / (m - 1.0)), alpha=f)
+    update_running_stats(bn, mean, var, x.shape[0])
     return y
 
 
 def hip_refusal(model: nn.Module, planes: Optional[torch.Tensor] = None, path: str = "hip") -> Optional[str]:
     """Why `model` (and `planes`) cannot take the "hip" path (or, path="bf16", the bf16 one), or None if it can."""
-    p = next(model.parameters())
-    if p.device.type != "cuda":
-        return f"the model is on {p.device}, not on a HIP device"
-    if any(q.dtype != torch.float32 for q in model.parameters()):
-        return f"the model is {p.dtype}, the kernels are f32" if path == "hip" else f"the model is {p.dtype}, the master parameters must be f32"
-    c = model.config.conv_filter_size
-    if path == "bf16" and c % 32:
-        return f"conv_filter_size {c} is not a multiple of 32 (c4_linear_bf16 needs F = 42 C to be a multiple of 192)"
-    if c % 16:
-        return f"conv_filter_size {c} is not a multiple of 16 (F = 42 C must be a multiple of 32)"
-    if not model.training:
-        return "the model is in eval mode (the kernels are the train-mode block)"
-    if planes is not None and (planes.device != p.device or planes.dtype != torch.float32):
-        return f"the batch is {planes.dtype} on {planes.device}, the model f32 on {p.device}"
-    return None
+    def shape(c: int) -> Optional[str]:
+        if path == "bf16" and c % 32:
+            return f"conv_filter_size {c} is not a multiple of 32 (c4_linear_bf16 needs F = 42 C to be a multiple of 192)"
+        if c % 16:
+            return f"conv_filter_size {c} is not a multiple of 16 (F = 42 C must be a multiple of 32)"
+        return None
+
+    not_f32 = "the model is {dtype}, the kernels are f32" if path == "hip" else "the model is {dtype}, the master parameters must be f32"
+    return kernel_refusal(model, planes, not_f32, shape, train_mode_of="block")
 
 
 # What heads="auto" means where "hip" is possible: the path the recorded whole-step measurement shows faster at the default shape
@@ -259,8 +244,12 @@ def forward_train(model: nn.Module, planes: torch.Tensor, heads: str = "auto", t
     multiple of 16) or to "bf16" (the same, a multiple of 32; bf16 mixed precision), else the plain module forward.  tower: "torch" (the
     module's convolutions), "hip" (train_tower.tower_forward: the tower forward and backward on the deterministic f32 kernels; ValueError
     where they cannot run) or "auto" (train_tower.AUTO_TOWER)."""
-    path = resolve_heads(model, heads, planes)
-    tower_path = resolve_tower(model, tower, planes)
+    return forward_resolved(model, planes, resolve_heads(model, heads, planes), resolve_tower(model, tower, planes))
+
+
+def forward_resolved(model: nn.Module, planes: torch.Tensor, path: str, tower_path: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`forward_train` on paths already resolved (`resolve_heads`'s and `resolve_tower`'s answers), with no check of its own: what a
+    training step calls, so that a step does not walk the model's parameters on the host."""
     if path == "torch" and tower_path == "torch":
         return model(planes)
     if tower_path == "hip":

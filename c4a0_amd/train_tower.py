@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import check, lib
+from .train_common import cuda_stream, kernel_refusal, update_running_stats
 
 TOWERS = ("auto", "hip", "torch")
 
@@ -26,10 +27,6 @@ TOWERS = ("auto", "hip", "torch")
 # convolutions, a whole step under the graph is a tie (1.886 ms against 1.897 ms) and the eager tower loses to its host side
 # (tools/train_rate.py --tower, profiles/train_rate_tower.json), so the default stays the stock tower.
 AUTO_TOWER = "torch"
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def work_bytes(n_boards: int, c: int) -> int:
@@ -82,7 +79,7 @@ class Conv0Function(torch.autograd.Function):
         b, c, dev = planes.shape[0], weight.shape[0], planes.device
         planes = planes.contiguous()
         z = torch.empty((42 * b, c), dtype=torch.float32, device=dev)
-        check(lib().c4_train_conv0_f32(planes.data_ptr(), pack_conv0(weight).data_ptr(), bias.data_ptr(), z.data_ptr(), b, c, _stream(dev)))
+        check(lib().c4_train_conv0_f32(planes.data_ptr(), pack_conv0(weight).data_ptr(), bias.data_ptr(), z.data_ptr(), b, c, cuda_stream(dev)))
         ctx.save_for_backward(planes)
         ctx.c = c
         return z
@@ -95,7 +92,7 @@ class Conv0Function(torch.autograd.Function):
         dw0 = torch.empty((c, 32), dtype=torch.float32, device=dev)
         db = torch.empty(c, dtype=torch.float32, device=dev)
         work = _work(b, c, dev)
-        check(lib().c4_train_conv0_wgrad_f32(dz.data_ptr(), planes.data_ptr(), dw0.data_ptr(), db.data_ptr(), b, c, work.data_ptr(), _stream(dev)))
+        check(lib().c4_train_conv0_wgrad_f32(dz.data_ptr(), planes.data_ptr(), dw0.data_ptr(), db.data_ptr(), b, c, work.data_ptr(), cuda_stream(dev)))
         return None, unpack_conv0(dw0), db
 
 
@@ -108,7 +105,7 @@ class Conv3x3Function(torch.autograd.Function):
         b = x.shape[0] // 42
         x = x.contiguous()
         z = torch.empty_like(x)
-        check(lib().c4_train_conv3x3_f32(x.data_ptr(), pack_conv3x3(weight).data_ptr(), bias.data_ptr(), z.data_ptr(), b, c, _stream(dev)))
+        check(lib().c4_train_conv3x3_f32(x.data_ptr(), pack_conv3x3(weight).data_ptr(), bias.data_ptr(), z.data_ptr(), b, c, cuda_stream(dev)))
         ctx.save_for_backward(x, weight)
         return z
 
@@ -117,7 +114,7 @@ class Conv3x3Function(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         c, dev = weight.shape[0], x.device
         b = x.shape[0] // 42
-        L, s = lib(), _stream(dev)
+        L, s = lib(), cuda_stream(dev)
         dz = dz.contiguous()
         dx = None
         if ctx.needs_input_grad[0]:
@@ -145,7 +142,7 @@ class Bn2dReluResFunction(torch.autograd.Function):
         var = torch.empty(c, dtype=torch.float32, device=dev)
         work = _work(b, c, dev)
         check(lib().c4_train_bn2d_relu_res_fwd_f32(z.data_ptr(), a.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, b, c, y.data_ptr(),
-                                                   mean.data_ptr(), var.data_ptr(), work.data_ptr(), _stream(dev)))
+                                                   mean.data_ptr(), var.data_ptr(), work.data_ptr(), cuda_stream(dev)))
         ctx.save_for_backward(z, mean, var, gamma, beta)
         ctx.eps = eps
         ctx.mark_non_differentiable(mean, var)
@@ -162,7 +159,7 @@ class Bn2dReluResFunction(torch.autograd.Function):
         dbeta = torch.empty(c, dtype=torch.float32, device=dev)
         work = _work(b, c, dev)
         check(lib().c4_train_bn2d_relu_res_bwd_f32(dy.data_ptr(), z.data_ptr(), mean.data_ptr(), var.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                   ctx.eps, b, c, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), work.data_ptr(), _stream(dev)))
+                                                   ctx.eps, b, c, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), work.data_ptr(), cuda_stream(dev)))
         return dz, dy, dgamma, dbeta, None
 
 
@@ -170,13 +167,7 @@ def _bn2d_relu_res(bn: nn.BatchNorm2d, z: torch.Tensor, a: torch.Tensor) -> torc
     """a + relu(bn(z)) in train mode; the running statistics move exactly as `nn.BatchNorm2d` moves them (momentum 0.1, the UNBIASED
     variance var m / (m - 1) with m = 42 B, num_batches_tracked += 1)."""
     y, mean, var = Bn2dReluResFunction.apply(z, a, bn.weight, bn.bias, bn.eps)
-    if bn.track_running_stats and bn.running_mean is not None:
-        m = z.shape[0]
-        with torch.no_grad():
-            bn.num_batches_tracked += 1
-            f = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            bn.running_mean.mul_(1.0 - f).add_(mean, alpha=f)
-            bn.running_var.mul_(1.0 - f).add_(var * (m / (m - 1.0)), alpha=f)
+    update_running_stats(bn, mean, var, z.shape[0])
     return y
 
 
@@ -198,19 +189,10 @@ def tower_forward(conv: nn.Sequential, planes: torch.Tensor) -> torch.Tensor:
 
 def tower_refusal(model: nn.Module, planes: Optional[torch.Tensor] = None) -> Optional[str]:
     """Why `model` (and `planes`) cannot take tower="hip", or None if it can."""
-    p = next(model.parameters())
-    if p.device.type != "cuda":
-        return f"the model is on {p.device}, not on a HIP device"
-    if any(q.dtype != torch.float32 for q in model.parameters()):
-        return f"the model is {p.dtype}, the kernels are f32"
-    c = model.config.conv_filter_size
-    if c % 16 or not 16 <= c <= 64:
-        return f"conv_filter_size {c} is not a multiple of 16 up to 64"
-    if not model.training:
-        return "the model is in eval mode (the kernels are the train-mode tower)"
-    if planes is not None and (planes.device != p.device or planes.dtype != torch.float32):
-        return f"the batch is {planes.dtype} on {planes.device}, the model f32 on {p.device}"
-    return None
+    def shape(c: int) -> Optional[str]:
+        return f"conv_filter_size {c} is not a multiple of 16 up to 64" if c % 16 or not 16 <= c <= 64 else None
+
+    return kernel_refusal(model, planes, shape=shape, train_mode_of="tower")
 
 
 def resolve_tower(model: nn.Module, tower: str = "auto", planes: Optional[torch.Tensor] = None) -> str:

@@ -21,11 +21,11 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from . import train_graph
 from .nn import ConnectFourNet, ModelConfig
-from .train_heads import forward_train, resolve_heads
+from .train_common import EPS, loss  # noqa: F401  (`training.loss` and `training.EPS` are public)
+from .train_heads import resolve_heads
 from .train_tower import resolve_tower
-
-EPS = 1e-8  # nn.py:57: avoids log(0)
 
 
 @dataclass
@@ -57,45 +57,10 @@ def lr_for_gen(lr_schedule: Dict[int, float], gen_n: int) -> float:
     return lr
 
 
-def loss(model_outputs, batch):
-    """The reference's training loss (nn.py:160-181) of `model_outputs` = (policy log-probabilities [B, 7], q_penalty [B],
-    q_no_penalty [B]) on `batch` = (pos, policy target, q_penalty target, q_no_penalty target):
-
-        policy_kl = mean_b sum_j (t + EPS) (log(t + EPS) - logp)      [assumption]
-        total     = policy_kl + mean (q_penalty - target)^2 + mean (q_no_penalty - target)^2
-
-    [assumption] policy_kl restates torchmetrics' `KLDivergence(log_prob=True)` called as (log(targets + EPS), prediction) from its
-    documented definition -- sum_j p_j (log p_j - log q_j) per row with p = exp of the first argument, mean over rows;
-    torchmetrics itself was not available to compare against.
-
-    Returns (total, policy_kl, q_penalty_mse, q_no_penalty_mse)."""
-    logp, q_pen, q_nopen = model_outputs
-    _pos, policy_t, q_pen_t, q_nopen_t = batch
-    t = policy_t + EPS
-    policy_kl = (t * (torch.log(t) - logp)).sum(dim=1).mean()
-    q_pen_mse = ((q_pen - q_pen_t) ** 2).mean()
-    q_nopen_mse = ((q_nopen - q_nopen_t) ** 2).mean()
-    return policy_kl + q_pen_mse + q_nopen_mse, policy_kl, q_pen_mse, q_nopen_mse
-
-
 def evaluate_loss(model, data, batch_size: int) -> float:
-    """The sample mean of `loss` over `data` in eval mode (what Lightning's batch-size-weighted epoch mean of val_loss equals).
-    The model's mode is restored."""
-    was_training = model.training
-    model.eval()
-    n = data[0].shape[0]
-    total = 0.0
-    with torch.no_grad():
-        for i in range(0, n, batch_size):
-            b = tuple(t[i:i + batch_size] for t in data)
-            total += float(loss(model(b[0]), b)[0]) * b[0].shape[0]
-    model.train(was_training)
-    return total / n
-
-
-def evaluate_loss_device(model, data, batch_size: int) -> float:
-    """`evaluate_loss` with the sum kept on the device in float64 and read once: the same products in the same order, so the same
-    value, with one synchronisation a pass instead of one a batch."""
+    """The sample mean of `loss` over `data` in eval mode (what Lightning's batch-size-weighted epoch mean of val_loss equals).  The
+    sum is kept in float64 on the data's device and read once: one synchronisation a pass, not one a batch.  The model's mode is
+    restored."""
     was_training = model.training
     model.eval()
     n = data[0].shape[0]
@@ -108,68 +73,6 @@ def evaluate_loss_device(model, data, batch_size: int) -> float:
     return float(total) / n
 
 
-def _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph, tower="torch"):
-    """`fit` with `HipAdam`: the same loop, eagerly (graph=False) or with every step a replay of a captured HIP graph (graph=True)."""
-    from .train_graph import HipAdam, graph_refusal
-
-    why = graph_refusal(model)
-    if why is not None:
-        raise ValueError(("graph=True" if graph else 'optimizer="hip"') + f": {why}")
-    val_loss_fn = val_loss_fn or (evaluate_loss_device if graph else evaluate_loss)
-    lr = lr_for_gen(cfg.lr_schedule, gen_n)
-    dev = train[0].device
-    gen = torch.Generator(device="cpu")
-    gen.manual_seed(int(seed))
-    n = train[0].shape[0]
-    model.train()
-    path = resolve_heads(model, heads, train[0])
-    tower_path = resolve_tower(model, tower, train[0])
-    opt = HipAdam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
-    try:
-        return _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph, tower_path)
-    finally:
-        opt.release()   # also when a step, a capture or val_loss_fn raises: the model does not keep gradients a dead table points at
-
-
-def _fit_hip_epochs(model, train, val, batch_size, lr, dev, gen, n, path, opt, max_epochs, patience, val_loss_fn, graph, tower_path="torch"):
-    from .train_graph import GraphedSteps
-
-    graphs = GraphedSteps(model, opt, path, train, tower_path) if graph else None
-    best_model, best_val, since_best, history = None, math.inf, 0, []
-    for epoch in range(max_epochs):
-        model.train()
-        perm = torch.randperm(n, generator=gen).to(dev)
-        total = graphs.total.zero_() if graph else torch.zeros((), dtype=torch.float64, device=dev)
-        seen = steps = 0
-        for i in range(0, n, batch_size):
-            idx = perm[i:i + batch_size]
-            if idx.shape[0] < 2:
-                continue
-            if graph:
-                graphs.run(idx)
-            else:
-                b = tuple(t[idx] for t in train)
-                opt.zero_grad()
-                step_loss = loss(forward_train(model, b[0], path, tower_path), b)[0]
-                step_loss.backward()
-                opt.step()
-                total += step_loss.detach().double() * idx.shape[0]
-            seen += idx.shape[0]
-            steps += 1
-        train_loss = float(total) / max(seen, 1)
-        val_loss = float(val_loss_fn(model, val, batch_size))
-        history.append({"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss, "lr": lr, "steps": steps})
-        if val_loss < best_val:
-            best_model, best_val, since_best = copy.deepcopy(model), val_loss, 0
-        else:
-            since_best += 1
-            if since_best >= patience:
-                break
-    if best_model is None:   # no epoch, or no finite val_loss: the model as it is
-        best_model = copy.deepcopy(model)
-    return best_model, best_val, history
-
-
 def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: int = 1337, heads: str = "auto", max_epochs: int = 100,
         patience: int = 10, val_loss_fn: Optional[Callable] = None, optimizer: str = "auto", graph: bool = False, tower: str = "auto"):
     """Train `model` in place on `train`, watching `val` (both tuples (pos, policy, q_penalty, q_no_penalty) of tensors on the
@@ -178,8 +81,9 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
     * Adam(lr = lr_for_gen(cfg.lr_schedule, gen_n), weight_decay = cfg.l2_reg): coupled L2, default betas and eps (nn.py:140-152).
     * Every epoch draws a fresh `torch.randperm` from a generator seeded once by `seed`; the last partial batch is kept.  A trailing
       batch of exactly ONE sample is skipped: BatchNorm in train mode cannot take it (the reference would raise there).
-    * Steps run in train mode through `forward_train(model, pos, heads)`; after every epoch val_loss is the sample mean of `loss`
-      over the whole of `val` in eval mode (`val_loss_fn(model, val, batch_size)` if given, else `evaluate_loss`).
+    * Steps run in train mode as `train_graph.train_step` on the paths `heads` and `tower` resolve to, once, before the first epoch;
+      after every epoch val_loss is the sample mean of `loss` over the whole of `val` in eval mode (`val_loss_fn(model, val,
+      batch_size)` if given, else `evaluate_loss`).
     * A deep copy of the model with the strictly lowest val_loss is kept (utils.py:79-82).  Training stops after `patience`
       consecutive epochs without a strictly lower val_loss (Lightning's EarlyStopping(patience, min_delta=0): a tie is no
       improvement) or after `max_epochs` epochs.  max_epochs = 100 and patience = 10 are the values the reference hard-codes.
@@ -187,7 +91,7 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
     optimizer: "torch" is `torch.optim.Adam`; "hip" is `train_graph.HipAdam`, the same update as one launch with its state and step
     count on the device; "auto" is "torch" without a graph and "hip" with one.  graph=True (opt-in; an f32 model on a HIP device and
     optimizer "hip", else ValueError) captures one whole step per batch shape -- the full batch and the epoch's last partial one -- as a
-    HIP graph and replays it (`train_graph.GraphedTrainStep`); the validation pass then sums on the device (`evaluate_loss_device`).
+    HIP graph and replays it (`train_graph.GraphedSteps`); without it the steps run eagerly (`train_graph.EagerSteps`).
     History and return values mean the same on every path.
 
     tower: `forward_train`'s -- "torch" (the stock convolutions), "hip" (opt-in: the tower forward and backward on the deterministic
@@ -196,13 +100,13 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
 
     Returns (best_model, best_val_loss, history), history = one dict per epoch: epoch, train_loss (the sample mean of the steps'
     losses), val_loss, lr, steps."""
-    from .train_graph import resolve_optimizer
-
-    if resolve_optimizer(optimizer, graph) == "hip":
-        return _fit_hip(model, train, val, batch_size, gen_n, cfg, seed, heads, max_epochs, patience, val_loss_fn, graph, tower)
+    optimizer = train_graph.resolve_optimizer(optimizer, graph)
+    if optimizer == "hip":
+        why = train_graph.graph_refusal(model)
+        if why is not None:
+            raise ValueError(("graph=True" if graph else 'optimizer="hip"') + f": {why}")
     val_loss_fn = val_loss_fn or evaluate_loss
     lr = lr_for_gen(cfg.lr_schedule, gen_n)
-    opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
     dev = train[0].device
     gen = torch.Generator(device="cpu")
     gen.manual_seed(int(seed))
@@ -210,35 +114,40 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
     model.train()
     path = resolve_heads(model, heads, train[0])
     tower_path = resolve_tower(model, tower, train[0])
-    best_model, best_val, since_best, history = None, math.inf, 0, []
-    for epoch in range(max_epochs):
-        model.train()
-        perm = torch.randperm(n, generator=gen).to(dev)
-        total = torch.zeros((), dtype=torch.float64, device=dev)
-        seen = steps = 0
-        for i in range(0, n, batch_size):
-            idx = perm[i:i + batch_size]
-            if idx.shape[0] < 2:
-                continue
-            b = tuple(t[idx] for t in train)
-            opt.zero_grad(set_to_none=True)
-            step_loss = loss(forward_train(model, b[0], path, tower_path), b)[0]
-            step_loss.backward()
-            opt.step()
-            total += step_loss.detach().double() * idx.shape[0]
-            seen += idx.shape[0]
-            steps += 1
-        val_loss = float(val_loss_fn(model, val, batch_size))
-        history.append({"epoch": epoch, "train_loss": float(total) / max(seen, 1), "val_loss": val_loss, "lr": lr, "steps": steps})
-        if val_loss < best_val:
-            best_model, best_val, since_best = copy.deepcopy(model), val_loss, 0
-        else:
-            since_best += 1
-            if since_best >= patience:
-                break
-    if best_model is None:   # no epoch, or no finite val_loss: the model as it is
-        best_model = copy.deepcopy(model)
-    return best_model, best_val, history
+    if optimizer == "hip":   # looked up at call time: the tests put a recording subclass there
+        opt = train_graph.HipAdam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
+    try:
+        steps = (train_graph.GraphedSteps if graph else train_graph.EagerSteps)(model, opt, path, train, tower_path)
+        best_model, best_val, since_best, history = None, math.inf, 0, []
+        for epoch in range(max_epochs):
+            model.train()
+            perm = torch.randperm(n, generator=gen).to(dev)
+            steps.reset()
+            seen = n_steps = 0
+            for i in range(0, n, batch_size):
+                idx = perm[i:i + batch_size]
+                if idx.shape[0] < 2:
+                    continue
+                steps.run(idx)
+                seen += idx.shape[0]
+                n_steps += 1
+            train_loss = float(steps.total) / max(seen, 1)
+            val_loss = float(val_loss_fn(model, val, batch_size))
+            history.append({"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss, "lr": lr, "steps": n_steps})
+            if val_loss < best_val:
+                best_model, best_val, since_best = copy.deepcopy(model), val_loss, 0
+            else:
+                since_best += 1
+                if since_best >= patience:
+                    break
+        if best_model is None:   # no epoch, or no finite val_loss: the model as it is
+            best_model = copy.deepcopy(model)
+        return best_model, best_val, history
+    finally:
+        if optimizer == "hip":
+            opt.release()   # also when a step, a capture or val_loss_fn raises: the model does not keep gradients a dead table points at
 
 
 # metadata.json: the reference's fields (training.py:30-39), then what this package adds

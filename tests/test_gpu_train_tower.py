@@ -135,6 +135,77 @@ def _fit(**kwargs):
     return student.state_dict(), best_val, history
 
 
+def _small(rows: int):
+    """the recipe's student on its first `rows` training samples (at batch 64: 130 is 64 + 64 + 2, the smallest batch a kernel takes;
+    129 leaves a tail of one, which is skipped) and 64 validation samples"""
+    student, train, val = R.problem()
+    return student.to(DEV), tuple(t[:rows].to(DEV) for t in train), tuple(t[:64].to(DEV) for t in val)
+
+
+def _small_fit(rows: int, **kwargs):
+    student, train, val = _small(rows)
+    _best, _best_val, history = T.fit(student, train, val, 64, 1, R.TRAIN_CONFIG, seed=1337, heads="hip", tower="hip", max_epochs=2, **kwargs)
+    return student.state_dict(), history
+
+
+def _small_by_hand(rows: int, make_optimiser):
+    """`fit`'s loop restated: 2 epochs of steps through the public forward_train, the sums in float64 in step order"""
+    student, train, val = _small(rows)
+    opt = make_optimiser(student.parameters(), lr=2e-3, weight_decay=4e-4)
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(1337)
+    history = []
+    try:
+        for epoch in range(2):
+            student.train()
+            perm = torch.randperm(rows, generator=gen).to(DEV)
+            total, seen, steps = 0.0, 0, 0
+            for i in range(0, rows, 64):
+                idx = perm[i:i + 64]
+                if len(idx) < 2:
+                    continue
+                b = tuple(t[idx] for t in train)
+                opt.zero_grad()
+                step_loss = T.loss(forward_train(student, b[0], "hip", "hip"), b)[0]
+                step_loss.backward()
+                opt.step()
+                total += float(step_loss.detach()) * len(idx)
+                seen += len(idx)
+                steps += 1
+            student.eval()
+            with torch.no_grad():
+                val_loss = float(T.loss(student(val[0]), val)[0])      # one batch of 64: its loss is the sample mean (x 64 / 64 is exact)
+            history.append({"epoch": epoch, "train_loss": total / seen, "val_loss": val_loss, "lr": 2e-3, "steps": steps})
+    finally:
+        if hasattr(opt, "release"):      # HipAdam: the student does not keep gradients a dead table points at, as `fit` guarantees
+            opt.release()
+    return student.state_dict(), history
+
+
+def _assert_same_run(name: str, got, want):
+    different = [k for k, v in want[0].items() if not equal_bits(v, got[0][k])]
+    assert list(got[0]) == list(want[0]) and not different, (name, different)
+    assert got[1] == want[1], (name, got[1], want[1])
+
+
+def test_fit_with_torch_adam_is_byte_for_byte_a_hand_written_loop():
+    want = _small_by_hand(130, torch.optim.Adam)
+    assert [h["steps"] for h in want[1]] == [3, 3]
+    assert not torch.equal(R.problem()[0].state_dict()["conv.0.weight"], want[0]["conv.0.weight"].cpu())        # trained at all
+    _assert_same_run("optimizer=torch", _small_fit(130, optimizer="torch"), want)
+
+
+@pytest.mark.parametrize("rows,steps", [(130, 3), (129, 2)])
+def test_fit_with_hip_adam_eagerly_and_from_the_graph_is_byte_for_byte_a_hand_written_loop(rows, steps):
+    from c4a0_amd import train_graph
+
+    want = _small_by_hand(rows, train_graph.HipAdam)
+    assert [h["steps"] for h in want[1]] == [steps, steps]
+    assert not torch.equal(R.problem()[0].state_dict()["conv.0.weight"], want[0]["conv.0.weight"].cpu())
+    _assert_same_run("optimizer=hip", _small_fit(rows, optimizer="hip"), want)
+    _assert_same_run("graph=True", _small_fit(rows, graph=True), want)
+
+
 def test_a_whole_fit_repeats_itself_byte_for_byte_eagerly_and_from_the_graph(monkeypatch):
     monkeypatch.setattr(torch.backends.cudnn, "deterministic", False)
     runs = {"A": _fit(optimizer="hip"), "A'": _fit(optimizer="hip"), "G": _fit(graph=True)}

@@ -105,6 +105,40 @@ def test_a_trailing_batch_of_one_sample_is_skipped():
     assert history[0]["steps"] == 2                              # 4 + 3: the partial batch is kept
 
 
+def test_fit_is_byte_for_byte_a_hand_written_loop():
+    """9 samples at batch 4 (two steps and a skipped tail of one), 2 epochs: `fit` against the loop restated here"""
+    cfg, epochs, seed = T.TrainConfig({0: 1e-2}, 4e-4), 2, 5
+    model, data = _tiny()
+    data = tuple(t[:9] for t in data)
+    mine = copy.deepcopy(model)
+    _best, _best_val, history = T.fit(model, data, data, 4, 0, cfg, seed=seed, heads="torch", optimizer="torch", max_epochs=epochs)
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(seed)
+    opt = torch.optim.Adam(mine.parameters(), lr=1e-2, weight_decay=4e-4)
+    means = []
+    for _epoch in range(epochs):
+        mine.train()
+        perm = torch.randperm(9, generator=gen)
+        total, seen = np.float64(0.0), 0
+        for i in range(0, 9, 4):
+            idx = perm[i:i + 4]
+            if len(idx) < 2:
+                continue
+            b = tuple(t[idx] for t in data)
+            opt.zero_grad()
+            step_loss = T.loss(mine(b[0]), b)[0]
+            step_loss.backward()
+            opt.step()
+            total += np.float64(step_loss.detach().item()) * len(idx)
+            seen += len(idx)
+        means.append(float(total) / seen)
+    assert len(history) == epochs and [h["steps"] for h in history] == [2, 2]
+    assert [h["train_loss"] for h in history] == means
+    a, b = model.state_dict(), mine.state_dict()
+    assert list(a) == list(b) and all(a[k].numpy().tobytes() == b[k].numpy().tobytes() for k in a)
+    assert not torch.equal(a["conv.0.weight"], _tiny()[0].state_dict()["conv.0.weight"])     # the steps moved the model at all
+
+
 def test_heads_hip_is_refused_by_name_on_the_cpu():
     model, data = _tiny()
     with pytest.raises(ValueError, match="not on a HIP device"):
