@@ -122,6 +122,7 @@ class AdamSegment(C.Structure):
 
 TOWER_CHUNK_BOARDS = 16   # include/c4a0_hip.h C4_TRAIN_TOWER_CHUNK_BOARDS: the rows of a training-tower reduction are split by 16 boards
 ADAM_BLOCK_ELEMS = 4096   # include/c4a0_hip.h C4_ADAM_BLOCK_ELEMS == c4_train_adam_block_elems()
+OUT_CHUNK_ROWS = 64       # include/c4a0_hip.h C4_TRAIN_OUT_CHUNK_ROWS == c4_train_out_chunk_rows()
 
 SOLVE_FULL_COLUMN, SOLVE_UNSOLVED = -1000, -32768   # include/c4a0_hip.h C4_SOLVE_FULL_COLUMN, C4_SOLVE_UNSOLVED
 SOLVER_TT_ENTRIES = 1 << 24                         # C4_SOLVER_TT_ENTRIES
@@ -218,6 +219,12 @@ SIGNATURES = {
                                             _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "c4_train_adam_f32": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "c4_train_adam_block_elems": (C.c_int, []),
+    "c4_train_out_work_bytes": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_uint64)]),
+    "c4_train_out_chunk_rows": (C.c_int, []),
+    "c4_train_out_loss_fwd": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32,
+                                        _vp, _vp, _vp, _vp, _vp]),
+    "c4_train_out_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp,
+                                        C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c4_quantize_bf16_fp8": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _vp]),
     "c4_linear_fp8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                 C.c_uint32, _vp]),

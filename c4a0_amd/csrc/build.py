@@ -22,7 +22,7 @@ OUT = os.path.join(PKG, "libc4a0_hip.so")
 SRCS = [os.path.join(HERE, f) for f in (
     "c4_session.hip", "c4_session_maint.hip", "c4_session_callback.hip", "c4_session_readout.hip", "c4_session_route.hip", "c4_elementwise.hip",
     "c4_conv_tower.hip", "c4_head_gemm.hip", "c4_results_host.hip", "c4_selfplay_host.hip", "c4_f32_net.hip", "c4_fp8_gemm.hip", "c4_solver.hip",
-    "c4_train.hip", "c4_train_tower.hip", "c4_train_bf16.hip", "c4_train_adam.hip", "c4_builtin_players.hip")]
+    "c4_train.hip", "c4_train_tower.hip", "c4_train_bf16.hip", "c4_train_adam.hip", "c4_train_out.hip", "c4_builtin_players.hip")]
 DEPS = SRCS + [os.path.join(HERE, f) for f in (
     "c4_tree.hpp", "c4_session_impl.hpp", "c4_device.hpp", "c4_host.hpp", "c4_head_out.hpp", "c4_timeline.hpp", "c4_grouped.hpp", "c4_solver_core.hpp",
     "c4_solver_split.hpp", "c4_builtin.hpp")] + [

@@ -19,8 +19,9 @@ import torch.nn as nn
 
 from ._lib import ADAM_BLOCK_ELEMS, AdamSegment, check, lib
 from .session import capture
-from .train_common import cuda_stream, kernel_refusal, loss
-from .train_heads import forward_resolved, resolve_heads
+from .train_common import cuda_stream, kernel_refusal
+from .train_heads import resolve_heads, step_losses
+from .train_out import resolve_outputs
 from .train_tower import resolve_tower
 
 OPTIMIZERS = ("auto", "torch", "hip")
@@ -111,15 +112,16 @@ class HipAdam:
             p.grad = None
 
 
-def train_step(model: nn.Module, opt, batch: Sequence[torch.Tensor], heads_path: str, tower_path: str) -> torch.Tensor:
-    """THE optimiser step of training on `batch` = (pos, policy, q_penalty, q_no_penalty), on resolved paths: zero_grad, forward, `loss`,
-    backward, `opt.step()`.  Returns the step's loss, detached.  `torch.optim.Adam` drops its gradients; `HipAdam.zero_grad()` zeroes
+def train_step(model: nn.Module, opt, batch: Sequence[torch.Tensor], heads_path: str, tower_path: str, outputs_path: str = "torch") -> torch.Tensor:
+    """THE optimiser step of training on `batch` = (pos, policy, q_penalty, q_no_penalty), on resolved paths: zero_grad, the forward and the
+    loss (`train_heads.step_losses`: with outputs_path "torch" `loss(forward_resolved(...))`, with "hip" train_out's kernels), backward,
+    `opt.step()`.  Returns the step's loss, detached.  `torch.optim.Adam` drops its gradients; `HipAdam.zero_grad()` zeroes
     its persistent ones in place."""
     if isinstance(opt, torch.optim.Optimizer):
         opt.zero_grad(set_to_none=True)
     else:
         opt.zero_grad()
-    step_loss = loss(forward_resolved(model, batch[0], heads_path, tower_path), batch)[0]
+    step_loss = step_losses(model, batch, heads_path, tower_path, outputs_path)[0]
     step_loss.backward()
     opt.step()
     return step_loss.detach()
@@ -129,22 +131,23 @@ class EagerSteps:
     """The steps of one `fit` run eagerly, with either optimiser: `run(idx)` gathers the batch and takes `train_step`; `total` (a float64
     device scalar, a fresh zero after every `reset()`) is the epoch's running sum of loss * rows."""
 
-    def __init__(self, model: nn.Module, opt, heads_path: str, train: Sequence[torch.Tensor], tower_path: str):
+    def __init__(self, model: nn.Module, opt, heads_path: str, train: Sequence[torch.Tensor], tower_path: str, outputs_path: str = "torch"):
         self.model, self.opt, self.heads_path, self.tower_path, self.train = model, opt, heads_path, tower_path, train
+        self.outputs_path = outputs_path
         self.reset()
 
     def reset(self) -> None:
         self.total = torch.zeros((), dtype=torch.float64, device=self.train[0].device)
 
     def run(self, idx: torch.Tensor) -> None:
-        step_loss = train_step(self.model, self.opt, tuple(t[idx] for t in self.train), self.heads_path, self.tower_path)
+        step_loss = train_step(self.model, self.opt, tuple(t[idx] for t in self.train), self.heads_path, self.tower_path, self.outputs_path)
         self.total += step_loss.double() * idx.shape[0]
 
 
 class GraphedTrainStep:
     """One optimiser step of `model` on `batch_size` rows of `train` as a HIP graph.  The graph holds the gather of the batch from the
-    training tensors by the static index buffer, `train_step` on heads_path and tower_path (checked once, here, as `forward_train` checks
-    them) and `total += loss * rows` (`total`: a float64 device scalar, the epoch's running sum; one is made if none is given).
+    training tensors by the static index buffer, `train_step` on heads_path, tower_path and outputs_path (checked once, here, as
+    `forward_train` and `loss_train` check them) and `total += loss * rows` (`total`: a float64 device scalar, the epoch's running sum; one is made if none is given).
     `run(idx)` copies the indices into the static buffer and replays: nothing else happens on the host.
 
     Before the capture WARMUP_STEPS eager steps run on the capture's side stream, because the vendor libraries initialise lazily; the
@@ -152,7 +155,7 @@ class GraphedTrainStep:
     restored in place after them, and a capture executes nothing: the first replay is the first step."""
 
     def __init__(self, model: nn.Module, opt: HipAdam, heads_path: str, batch_size: int, train: Sequence[torch.Tensor],
-                 total: Optional[torch.Tensor] = None, tower_path: str = "torch"):
+                 total: Optional[torch.Tensor] = None, tower_path: str = "torch", outputs_path: str = "torch"):
         why = graph_refusal(model)
         if why is not None:
             raise ValueError(f"graph=True: {why}")
@@ -161,7 +164,9 @@ class GraphedTrainStep:
         dev = opt.device
         self.train = tuple(train)
         heads_path, tower_path = resolve_heads(model, heads_path, self.train[0]), resolve_tower(model, tower_path, self.train[0])
+        outputs_path = resolve_outputs(model, outputs_path, self.train[0])
         self.model, self.opt, self.heads_path, self.tower_path, self.batch_size = model, opt, heads_path, tower_path, int(batch_size)
+        self.outputs_path = outputs_path
         self.total = total if total is not None else torch.zeros((), dtype=torch.float64, device=dev)
         self.idx = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)
         self.batch = tuple(torch.empty((self.batch_size,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in self.train)
@@ -170,7 +175,7 @@ class GraphedTrainStep:
         def step():
             for src, dst in zip(self.train, self.batch):
                 torch.index_select(src, 0, self.idx, out=dst)
-            self.total += train_step(model, opt, self.batch, heads_path, tower_path).double() * self.batch_size
+            self.total += train_step(model, opt, self.batch, heads_path, tower_path, outputs_path).double() * self.batch_size
 
         keep = [t for t in list(model.parameters()) + list(model.buffers()) + opt.state() + [self.total]]
         current = torch.cuda.current_stream(dev)
@@ -199,8 +204,10 @@ class GraphedSteps:
     """The graphs of one `fit`: one `GraphedTrainStep` per batch shape, captured when the shape first comes (two at most: the full
     batch and the epoch's last partial one), all adding to one `total`."""
 
-    def __init__(self, model: nn.Module, opt: HipAdam, heads_path: str, train: Sequence[torch.Tensor], tower_path: str = "torch"):
+    def __init__(self, model: nn.Module, opt: HipAdam, heads_path: str, train: Sequence[torch.Tensor], tower_path: str = "torch",
+                 outputs_path: str = "torch"):
         self.model, self.opt, self.heads_path, self.tower_path, self.train = model, opt, heads_path, tower_path, train
+        self.outputs_path = outputs_path
         self.total = torch.zeros((), dtype=torch.float64, device=opt.device)
         self.by_rows: Dict[int, GraphedTrainStep] = {}
 
@@ -211,5 +218,6 @@ class GraphedSteps:
         rows = int(idx.shape[0])
         step = self.by_rows.get(rows)
         if step is None:
-            step = self.by_rows[rows] = GraphedTrainStep(self.model, self.opt, self.heads_path, rows, self.train, self.total, self.tower_path)
+            step = self.by_rows[rows] = GraphedTrainStep(self.model, self.opt, self.heads_path, rows, self.train, self.total, self.tower_path,
+                                                          self.outputs_path)
         step.run(idx)

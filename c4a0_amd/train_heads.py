@@ -5,7 +5,8 @@ the default network are over 90 % of a training step's FLOPs.  `HiddenBlockFunct
 `c4_linear_f32` (z = x W^T + b), `c4_train_bn_relu_fwd_f32`, `c4_train_bn_relu_bwd_f32`, `c4_train_linear_dgrad_f32` and
 `c4_train_linear_wgrad_f32` (c4a0_amd/csrc/c4_train.hip); `forward_train` walks the unchanged module tree of `c4a0_amd.nn.ConnectFourNet`
 and sends its hidden triples through it.  The tower, the two output layers, log-softmax, tanh and the loss stay stock PyTorch
-autograd by default; tower="hip" (opt-in) sends the tower through c4a0_amd/train_tower.py's deterministic kernels instead.
+autograd by default; tower="hip" (opt-in) sends the tower through c4a0_amd/train_tower.py's deterministic kernels instead, and
+outputs="hip" (opt-in; `step_losses`, `loss_train`) the output layers and the loss through c4a0_amd/train_out.py's.
 
 heads="bf16" (opt-in) runs the same triples in bf16 mixed precision: `HiddenBlockBf16Function` rounds x and the f32 master weights to
 bf16, takes all three products of a step -- forward x W^T, dgrad dz W, wgrad dz^T x -- from the bf16 MFMA GEMM `c4_linear_bf16`, and the
@@ -20,7 +21,8 @@ import torch
 import torch.nn as nn
 
 from ._lib import check, lib
-from .train_common import cuda_stream, kernel_refusal, update_running_stats
+from .train_common import cuda_stream, kernel_refusal, loss, update_running_stats
+from .train_out import out_losses, resolve_outputs
 from .train_tower import resolve_tower, tower_forward
 
 HEADS = ("auto", "hip", "torch", "bf16")
@@ -231,8 +233,7 @@ def _head(seq: nn.Sequential, x: torch.Tensor, path: str = "hip") -> torch.Tenso
     layers = list(seq)
     for i, layer in enumerate(layers):
         if isinstance(layer, nn.Sequential):
-            # a bf16 block that feeds another writes its y^T too: the next block's wgrad operand, without a cast launch
-            x = hidden_block(layer, x, path, emit_t=path == "bf16" and i + 1 < len(layers) and isinstance(layers[i + 1], nn.Sequential))
+            x = hidden_block(layer, x, path, emit_t=_emits_t(layers, i, path))
         else:
             x = layer(x.float() if x.dtype == torch.bfloat16 else x)   # the f32 output layer: autograd rounds its dx back to bf16
     return x
@@ -252,13 +253,58 @@ def forward_resolved(model: nn.Module, planes: torch.Tensor, path: str, tower_pa
     training step calls, so that a step does not walk the model's parameters on the host."""
     if path == "torch" and tower_path == "torch":
         return model(planes)
-    if tower_path == "hip":
-        x = tower_forward(model.conv, planes)
-    else:
-        x = model.conv(planes)
-        x = x.reshape(x.shape[0], -1)
+    x = _features(model, planes, tower_path)
     if path == "torch":
         q = model.fc_value(x)
         return model.fc_policy(x), q[:, 0], q[:, 1]
     q = _head(model.fc_value, x, path)
     return _head(model.fc_policy, x, path), q[:, 0], q[:, 1]
+
+
+def _features(model: nn.Module, planes: torch.Tensor, tower_path: str) -> torch.Tensor:
+    """the tower's output [B, 42 C] in the reference's flatten order, on the resolved tower path"""
+    if tower_path == "hip":
+        return tower_forward(model.conv, planes)
+    x = model.conv(planes)
+    return x.reshape(x.shape[0], -1)
+
+
+def _emits_t(layers, i: int, path: str) -> bool:
+    """a bf16 block that feeds another writes its y^T too: the next block's wgrad operand, without a cast launch"""
+    return path == "bf16" and i + 1 < len(layers) and isinstance(layers[i + 1], nn.Sequential)
+
+
+def _hidden(seq: nn.Sequential, x: torch.Tensor, path: str) -> Tuple[torch.Tensor, nn.Linear]:
+    """A head up to its output layer: (the last hidden activations -- `x` itself where the head has no hidden layer --, the output
+    `nn.Linear`).  The hidden blocks run as `_head` runs them (path "torch": the modules' own forward)."""
+    layers = list(seq)
+    for i, layer in enumerate(layers):
+        if not isinstance(layer, nn.Sequential):
+            return x, layer
+        if path == "torch":
+            x = layer(x)
+        else:
+            x = hidden_block(layer, x, path, emit_t=_emits_t(layers, i, path))
+    raise ValueError("the head has no output layer")
+
+
+def step_losses(model: nn.Module, batch, heads_path: str, tower_path: str, outputs_path: str = "torch"):
+    """THE loss of a training step on `batch` = (pos, policy, q_penalty, q_no_penalty), on resolved paths: (total, policy_kl,
+    q_penalty_mse, q_no_penalty_mse) with autograd.  outputs_path="torch": exactly `loss(forward_resolved(...), batch)`.
+    outputs_path="hip": the tower and every hidden block as `forward_resolved` runs them, then the two output layers, log-softmax, tanh
+    and the loss as one call of `train_out.OutLossFunction` on the heads' last activations (f32, or bf16 on the bf16 path: no cast to
+    f32 and no rounding back of dx by autograd)."""
+    if outputs_path == "torch":
+        return loss(forward_resolved(model, batch[0], heads_path, tower_path), batch)
+    x = _features(model, batch[0], tower_path)
+    xv, value_out = _hidden(model.fc_value, x, heads_path)
+    xp, policy_out = _hidden(model.fc_policy, x, heads_path)
+    return out_losses(policy_out, value_out, xp, xv, batch)
+
+
+def loss_train(model: nn.Module, batch, heads: str = "auto", tower: str = "auto", outputs: str = "auto"):
+    """`loss(model(pos), batch)` -- (total, policy_kl, q_penalty_mse, q_no_penalty_mse) -- with autograd, on the paths `heads`, `tower` and
+    `outputs` resolve to: the counterpart of `forward_train` for a whole step's loss.  outputs: "torch" (the stock output layers and
+    `loss`), "hip" (train_out's kernels; ValueError where they cannot run) or "auto" (train_out.AUTO_OUTPUTS)."""
+    planes = batch[0]
+    return step_losses(model, batch, resolve_heads(model, heads, planes), resolve_tower(model, tower, planes), resolve_outputs(model, outputs, planes))

@@ -24,7 +24,8 @@ import torch
 from . import train_graph
 from .nn import ConnectFourNet, ModelConfig
 from .train_common import EPS, loss  # noqa: F401  (`training.loss` and `training.EPS` are public)
-from .train_heads import resolve_heads
+from .train_heads import loss_train, resolve_heads  # noqa: F401  (`training.loss_train` is public)
+from .train_out import resolve_outputs
 from .train_tower import resolve_tower
 
 
@@ -74,14 +75,15 @@ def evaluate_loss(model, data, batch_size: int) -> float:
 
 
 def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: int = 1337, heads: str = "auto", max_epochs: int = 100,
-        patience: int = 10, val_loss_fn: Optional[Callable] = None, optimizer: str = "auto", graph: bool = False, tower: str = "auto"):
+        patience: int = 10, val_loss_fn: Optional[Callable] = None, optimizer: str = "auto", graph: bool = False, tower: str = "auto",
+        outputs: str = "auto"):
     """Train `model` in place on `train`, watching `val` (both tuples (pos, policy, q_penalty, q_no_penalty) of tensors on the
     model's device), as the reference's `trainer.fit` does (training.py:206-225):
 
     * Adam(lr = lr_for_gen(cfg.lr_schedule, gen_n), weight_decay = cfg.l2_reg): coupled L2, default betas and eps (nn.py:140-152).
     * Every epoch draws a fresh `torch.randperm` from a generator seeded once by `seed`; the last partial batch is kept.  A trailing
       batch of exactly ONE sample is skipped: BatchNorm in train mode cannot take it (the reference would raise there).
-    * Steps run in train mode as `train_graph.train_step` on the paths `heads` and `tower` resolve to, once, before the first epoch;
+    * Steps run in train mode as `train_graph.train_step` on the paths `heads`, `tower` and `outputs` resolve to, once, before the first epoch;
       after every epoch val_loss is the sample mean of `loss` over the whole of `val` in eval mode (`val_loss_fn(model, val,
       batch_size)` if given, else `evaluate_loss`).
     * A deep copy of the model with the strictly lowest val_loss is kept (utils.py:79-82).  Training stops after `patience`
@@ -97,6 +99,9 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
     tower: `forward_train`'s -- "torch" (the stock convolutions), "hip" (opt-in: the tower forward and backward on the deterministic
     kernels of `train_tower`; with heads="hip" and optimizer="hip" a fit then repeats itself byte for byte, eagerly and from the graph)
     or "auto" (`train_tower.AUTO_TOWER`: "torch").
+
+    outputs: `loss_train`'s -- "torch" (the stock output layers, log-softmax, tanh and `loss`, with their autograd), "hip" (opt-in: all of
+    that as one forward and one backward call of `train_out`'s deterministic kernels) or "auto" (`train_out.AUTO_OUTPUTS`: "torch").
 
     Returns (best_model, best_val_loss, history), history = one dict per epoch: epoch, train_loss (the sample mean of the steps'
     losses), val_loss, lr, steps."""
@@ -114,12 +119,13 @@ def fit(model, train, val, batch_size: int, gen_n: int, cfg: TrainConfig, seed: 
     model.train()
     path = resolve_heads(model, heads, train[0])
     tower_path = resolve_tower(model, tower, train[0])
+    outputs_path = resolve_outputs(model, outputs, train[0])
     if optimizer == "hip":   # looked up at call time: the tests put a recording subclass there
         opt = train_graph.HipAdam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
     else:
         opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=cfg.l2_reg)
     try:
-        steps = (train_graph.GraphedSteps if graph else train_graph.EagerSteps)(model, opt, path, train, tower_path)
+        steps = (train_graph.GraphedSteps if graph else train_graph.EagerSteps)(model, opt, path, train, tower_path, outputs_path)
         best_model, best_val, since_best, history = None, math.inf, 0, []
         for epoch in range(max_epochs):
             model.train()
@@ -274,12 +280,12 @@ def generation_tensors(games, device=None):
 def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_games: int, n_mcts_iterations: int, c_exploration: float,
                      c_ply_penalty: float, self_play_batch_size: int, training_batch_size: int, solver=None, heads: str = "auto", seed: int = 1337,
                      max_epochs: int = 100, patience: int = 10, timings: Optional[dict] = None, optimizer: str = "auto", graph: bool = False,
-                     tower: str = "auto", **play_kwargs) -> TrainingGen:
+                     tower: str = "auto", outputs: str = "auto", **play_kwargs) -> TrainingGen:
     """Train a new generation from `parent` (training.py:155-239): self-play with the parent's network, optionally the games'
     `solver_score(solver)`, the reference's train / validation split with mirror images, `fit` on a copy of the parent, and the new
     generation's folder.  solver: a `c4a0_amd.Solver` (None: no scoring).  play_kwargs go to `c4a0_amd.play_games`
-    (resident_games, dirichlet, ...).  timings (a dict) receives the wall seconds of play / split / train.  optimizer, graph and
-    tower are `fit`'s."""
+    (resident_games, dirichlet, ...).  timings (a dict) receives the wall seconds of play / split / train.  optimizer, graph,
+    tower and outputs are `fit`'s."""
     import time
 
     from . import GameMetadata
@@ -302,7 +308,8 @@ def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_gam
         torch.cuda.synchronize(device)
     t2 = time.perf_counter()
     best_model, best_val, _history = fit(copy.deepcopy(model), train, val, training_batch_size, parent.gen_n + 1, train_config, seed=seed,
-                                         heads=heads, max_epochs=max_epochs, patience=patience, optimizer=optimizer, graph=graph, tower=tower)
+                                         heads=heads, max_epochs=max_epochs, patience=patience, optimizer=optimizer, graph=graph, tower=tower,
+                                         outputs=outputs)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     t3 = time.perf_counter()
@@ -322,13 +329,14 @@ def train_single_gen(base_dir: str, device, parent: TrainingGen, n_self_play_gam
 
 def training_loop(base_dir: str, device, n_self_play_games: int, n_mcts_iterations: int, c_exploration: float, c_ply_penalty: float,
                   self_play_batch_size: int, training_batch_size: int, model_config: ModelConfig, max_gens: Optional[int] = None, solver=None,
-                  train_config: Optional[TrainConfig] = None, heads: str = "auto", tower: str = "auto", **kwargs) -> TrainingGen:
+                  train_config: Optional[TrainConfig] = None, heads: str = "auto", tower: str = "auto", outputs: str = "auto",
+                  **kwargs) -> TrainingGen:
     """Generation after generation (training.py:242-294) from the latest one of base_dir (generation 0 is created where there is
     none, with `model_config` and `train_config`), until gen_n reaches max_gens (None: for ever)."""
     gen = TrainingGen.load_latest_with_default(base_dir, n_mcts_iterations, c_exploration, c_ply_penalty, self_play_batch_size,
                                                training_batch_size, model_config, train_config)
     while True:
         gen = train_single_gen(base_dir, device, gen, n_self_play_games, n_mcts_iterations, c_exploration, c_ply_penalty, self_play_batch_size,
-                               training_batch_size, solver=solver, heads=heads, tower=tower, **kwargs)
+                               training_batch_size, solver=solver, heads=heads, tower=tower, outputs=outputs, **kwargs)
         if max_gens is not None and gen.gen_n >= max_gens:
             return gen

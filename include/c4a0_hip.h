@@ -991,6 +991,61 @@ int c4_train_adam_f32(const c4_adam_segment* table_dev, uint32_t n_segs, uint32_
                       double beta2, double eps, double weight_decay, void* stream);
 int c4_train_adam_block_elems(void); /* == C4_ADAM_BLOCK_ELEMS */
 
+/* ---- training: the output layers and the loss (c4a0_amd/train_out.py outputs="hip"; added functions only: C4_ABI_VERSION stays what
+ * it was) -----
+ * The end of a training step (nn.py:84-85, 98-99, 160-181): Linear(k, 7) + LogSoftmax on the policy head's last activations xp,
+ * Linear(k, 2) + Tanh on the value head's xv, the KL divergence against the policy targets, the two mean squared errors, and the
+ * gradients of all of it.  m >= 1 rows (m <= 2^30), k a multiple of 8 (k <= 2^20).  xp, xv [m][ldxp / ldxv] are f32, or bf16 where
+ * x_is_bf16 != 0 (widened exactly; all arithmetic is f32), and may be the same buffer; wp [7][k], bp [7], wv [2][k], bv [2], the
+ * targets policy_t [m][7], q_pen_t [m], q_nopen_t [m], out [m][9], dz [m][9], losses [4] and every gradient of a parameter are dense
+ * f32.  Row strides are multiples of 4 elements (f32) or 8 (bf16) and at least k; every array is 16-byte aligned (scale: 4 bytes).  A
+ * violation is C4_ERR_BAD_ARG with a c4_last_error_string that starts with the function's name, and nothing is launched.  No call
+ * allocates, copies or synchronises: each may be captured.  work_dev is the caller's, c4_train_out_work_bytes(m, k) bytes, its
+ * contents meaningless between calls.  The library is built with -ffp-contract=off: fma(a, b, c) is ONE rounding and appears only
+ * where it is written.  EPS = 1e-8f.
+ *
+ * The contract: every output is a fixed function of the inputs; each sum has ONE order, decided by (m, k) alone; no atomics, no
+ * counters: two calls give the same bytes.  A row's nine `out` values and nine `dz` values are a function of that row, the
+ * weights, k and (dz only) m: not of where the row lies.
+ *   dot        s = x[row] . w[j] over k columns: the columns are split into groups of 8 consecutive ones; lane l = 0..63 starts from +0
+ *              and takes the groups l, l + 64, l + 128, .. in ascending order, within a group s_l = fma(x[c], w[c], s_l) in ascending
+ *              column order; then for off = 32, 16, 8, 4, 2, 1: s_l += s_(l xor off), every lane at once.  The result is s_0.
+ *   forward    per row: z_j = dot(xp, wp_j) + bp_j (j = 0..6), u_c = dot(xv, wv_c) + bv_c (c = 0, 1);
+ *              mx = fmaxf over z_0 .. z_6 in order; se = sum_j expf(z_j - mx) from +0 in order; logp_j = (z_j - mx) - logf(se);
+ *              q_c = tanhf(u_c); t'_j = t_j + EPS; kl_row = fma(t'_j, logf(t'_j) - logp_j, kl_row) from +0 over j in order;
+ *              st = t'_0 + t'_1 + .. + t'_6 in order; d_0 = q_0 - q_pen_t, d_1 = q_1 - q_nopen_t; the row's terms are kl_row, d_0 d_0,
+ *              d_1 d_1.  out[row] = (logp_0 .. logp_6, q_0, q_1).  With fm = (float)m, the gradient of `total` at the pre-activations:
+ *              dz_j = fma(expf(logp_j), st, -t'_j) / fm;  dz_(7 + c) = ((2 d_c) (1 - q_c q_c)) / fm.
+ *   chunks     The rows are split into chunks of C4_TRAIN_OUT_CHUNK_ROWS = 64 rows; the last chunk holds what is left.
+ *              n_chunks = ceil(m / 64).  Per chunk every reduced element is ONE chain from +0 over the chunk's rows < m in ascending
+ *              order: a loss term s = s + term[row]; db_c[j] = db_c[j] + dz[row][j]; dW_c[j][c] = fma(dz[row][j], x[row][c], dW_c[j][c]).
+ *              A row past m enters no sum and no product.
+ *   2nd stage  per element: group g = 0..7 adds the chunks g, g + 8, g + 16, .. in order, starting FROM its first chunk; the result is
+ *              ((G_0 + G_1) + ..) + G_(min(8, n_chunks) - 1).
+ *   losses     kl, mse_pen, mse_nopen = 2nd stage(term) / fm;  losses = ((kl + mse_pen) + mse_nopen, kl, mse_pen, mse_nopen).
+ *   backward   with s = *scale_dev, read on the device only: dx[row][c] = (fma chain from +0 over the head's j in ascending order of
+ *              dz[row][j] w[j][c]) * s, written f32, or bf16 rounded ONCE (nearest, ties to even) where x_is_bf16; dW = 2nd stage(dW_c) * s,
+ *              db = 2nd stage(db_c) * s.  The policy head takes dz's columns 0..6, the value head 7 and 8.
+ * Non-finite input goes where this arithmetic sends it: a NaN in xp[row] reaches that row's seven logp and dz, its dxp row, kl,
+ * total, every element of dwp and dbp, and nothing of the value head; in xv[row] the same for q, dz_7, dz_8, both mean squared errors,
+ * total, dwv, dbv and the dxv row; a NaN policy target leaves `out` finite and reaches kl, total, the row's seven dz and what they
+ * reach.  fmaxf skips a NaN logit, whose expf is NaN all the same. */
+#define C4_TRAIN_OUT_CHUNK_ROWS 64
+/* *bytes_out = the bytes of work space either call below needs at (m, k): 4 max(4 m + 4 n_chunks, n_chunks (9 k + 12)). */
+int c4_train_out_work_bytes(uint32_t m, uint32_t k, uint64_t* bytes_out);
+int c4_train_out_chunk_rows(void); /* == C4_TRAIN_OUT_CHUNK_ROWS */
+/* out, dz (at an upstream gradient of 1) and losses from the activations, the parameters and the targets.  Two launches. */
+int c4_train_out_loss_fwd(const void* xp_dev, const void* xv_dev, uint32_t x_is_bf16, uint32_t ldxp, uint32_t ldxv, const float* wp_dev,
+                          const float* bp_dev, const float* wv_dev, const float* bv_dev, const float* policy_t_dev, const float* q_pen_t_dev,
+                          const float* q_nopen_t_dev, uint32_t m, uint32_t k, float* out_dev /*[m][9]*/, float* dz_dev /*[m][9]*/,
+                          float* losses_dev /*[4]*/, float* work_dev, void* stream);
+/* Every gradient of the output layers from dz and the upstream gradient of `total`, *scale_dev (one float in device memory).  dxp_dev and
+ * dxv_dev, [m][lddxp / lddxv] in the type of x, may each be NULL: that head's dx is then not written.  Two launches. */
+int c4_train_out_loss_bwd(const float* dz_dev, const float* scale_dev, const void* xp_dev, const void* xv_dev, uint32_t x_is_bf16, uint32_t ldxp,
+                          uint32_t ldxv, const float* wp_dev, const float* wv_dev, uint32_t m, uint32_t k, void* dxp_dev, void* dxv_dev,
+                          uint32_t lddxp, uint32_t lddxv, float* dwp_dev, float* dbp_dev, float* dwv_dev, float* dbv_dev, float* work_dev,
+                          void* stream);
+
 /* ---- exact solver ----------------------------------------------------------------------------------------------------------
  * What the reference gets from Pascal Pons' c4solver binary, its opening book and a rocksdb cache (rust/src/solver.rs): here a HIP
  * alpha-beta search with no binary, no book and no database.  These calls only ADD functions: C4_ABI_VERSION stays what it was.

@@ -1,6 +1,6 @@
 """The training kernels of the heads' hidden blocks beside the stock PyTorch ops, on the GPU -> profiles/train_rate.json.
 
-    python tools/train_rate.py [out.json] [--no-generation] [--max-epochs E] [--bf16 | --graph | --tower]
+    python tools/train_rate.py [out.json] [--no-generation] [--max-epochs E] [--bf16 | --graph | --tower | --outputs]
 
 (a) At m = 2 000 rows, F = 1 344 (the default network's heads at the reference's training batch): every kernel of c4_train.hip and
     the forward c4_linear_f32 beside the PyTorch op that does the same job on the same tensors -- F.linear, dz @ W, dz.T @ x (+ the
@@ -23,6 +23,10 @@
     channels): each call of c4_train_tower.hip beside the stock op it replaces on the same values (the stock side in its own NCHW layout);
     the tower's forward + backward alone, stock against train_tower.tower_forward; and the whole step for heads in {torch, bf16} x
     tower in {torch, hip}, eager with HipAdam and as a graph replay, beside the stock loop (torch.optim.Adam), all timed in turn.
+(g) --outputs: the opt-in outputs="hip" path -> profiles/train_rate_outputs.json.  At m = 2 000, k = 1 344, from f32 and from bf16
+    activations: the forward and the backward call of c4_train_out.hip beside the stock ops they replace on the same values, timed as one
+    group (F.linear x 2, log_softmax, tanh, loss and their autograd); and the whole step for heads in {torch, bf16} x outputs in
+    {torch, hip}, as a graph replay and eager with HipAdam, all timed in turn.
 Speed is recorded here, never asserted in a test."""
 import ctypes as C
 import json
@@ -404,6 +408,91 @@ def tower_leg():
     return out
 
 
+def outputs_leg():
+    """The opt-in outputs="hip" path.  (a) At m = 2 000, k = 1 344, from f32 and from bf16 activations: c4_train_out_loss_fwd and
+    c4_train_out_loss_bwd alone, the autograd Function over them forward + backward, and the stock ops they replace on the same values
+    as one group (F.linear x 2, log_softmax, tanh, loss; then with their autograd).  (b) The whole step of ModelConfig(1, 32, 4, 2) at
+    batch 2 000 for heads in {torch, bf16} x outputs in {torch, hip}, eager with HipAdam and as a graph replay, all timed in turn."""
+    from c4a0_amd import train_out as TO
+    from c4a0_amd import training as T
+    from c4a0_amd.nn import ConnectFourNet, ModelConfig
+    from c4a0_amd.train_graph import GraphedTrainStep, HipAdam, train_step
+
+    L, ck = _lib.lib(), _lib.check
+    g = torch.Generator().manual_seed(0)
+    m, k = M, FEAT
+    wp, wv = ((torch.rand(n, k, generator=g) * 2 - 1) / k ** 0.5 for n in (7, 2))
+    bp, bv = ((torch.rand(n, generator=g) * 2 - 1) / k ** 0.5 for n in (7, 2))
+    wp, bp, wv, bv = (t.to(dev) for t in (wp, bp, wv, bv))
+    tgt = (torch.softmax(torch.randn(m, 7, generator=g), 1).to(dev), (torch.rand(m, generator=g) * 2 - 1).to(dev),
+           (torch.rand(m, generator=g) * 2 - 1).to(dev))
+    out, dz = torch.empty((m, 9), device=dev), torch.empty((m, 9), device=dev)
+    losses, one = torch.empty(4, device=dev), torch.ones(4, device=dev)
+    dwp, dbp, dwv, dbv = torch.empty_like(wp), torch.empty_like(bp), torch.empty_like(wv), torch.empty_like(bv)
+    work = torch.empty(TO.work_bytes(m, k) // 4, device=dev)
+    res = {"shape": {"m": m, "k": k, "chunk_rows": _lib.OUT_CHUNK_ROWS, "work_bytes": TO.work_bytes(m, k)}, "calls": {}}
+    for name, dtype in (("f32", torch.float32), ("bf16", torch.bfloat16)):
+        # relu of a normal variable: what a hidden block hands over
+        xp, xv = (torch.relu(torch.randn(m, k, generator=g)).to(dev).to(dtype) for _ in range(2))
+        dxp, dxv = torch.empty_like(xp), torch.empty_like(xv)
+        is_bf16 = int(dtype == torch.bfloat16)
+        leaves = [t.clone().requires_grad_() for t in (xp, xv, wp, bp, wv, bv)]
+
+        def hip_fwd():
+            ck(L.c4_train_out_loss_fwd(p(xp), p(xv), is_bf16, k, k, p(wp), p(bp), p(wv), p(bv), p(tgt[0]), p(tgt[1]), p(tgt[2]), m, k, p(out), p(dz),
+                                       p(losses), p(work), stream()))
+
+        def hip_bwd():
+            ck(L.c4_train_out_loss_bwd(p(dz), p(one), p(xp), p(xv), is_bf16, k, k, p(wp), p(wv), m, k, p(dxp), p(dxv), k, k, p(dwp), p(dbp), p(dwv),
+                                       p(dbv), p(work), stream()))
+
+        def stock_losses():
+            # the bf16 path's f32 output layer reads x.float(); autograd rounds its dx back to bf16
+            logp = F.log_softmax(F.linear(leaves[0].float(), leaves[2], leaves[3]), dim=1)
+            q = torch.tanh(F.linear(leaves[1].float(), leaves[4], leaves[5]))
+            return T.loss((logp, q[:, 0], q[:, 1]), (None,) + tgt)
+
+        def torch_fwd():
+            stock_losses()
+
+        def torch_fwd_bwd():
+            torch.autograd.grad(stock_losses()[0], leaves)
+
+        def hip_function_fwd_bwd():
+            torch.autograd.grad(TO.OutLossFunction.apply(*leaves, *tgt)[0], leaves)
+
+        hip_fwd()
+        res["calls"][name] = alternating({"hip_fwd": hip_fwd, "hip_bwd": hip_bwd, "hip_function_fwd_bwd": hip_function_fwd_bwd,
+                                          "torch_fwd": torch_fwd, "torch_fwd_bwd": torch_fwd_bwd})
+        c = res["calls"][name]
+        c["hip_fwd_plus_bwd_us"] = c["hip_fwd"]["us"] + c["hip_bwd"]["us"]
+        c["x_bytes_read_per_call"] = 2 * m * k * xp.element_size()
+        c["hip_fwd_bytes_per_s"] = c["x_bytes_read_per_call"] / (c["hip_fwd"]["us"] * 1e-6)
+        c["hip_bwd_bytes_per_s"] = 2 * c["x_bytes_read_per_call"] / (c["hip_bwd"]["us"] * 1e-6)      # reads x, writes dx
+
+    cell = torch.randint(0, 3, (M, 6, 7), generator=g)
+    data = (torch.stack([cell == 1, cell == 2], 1).float().to(dev), torch.softmax(torch.randn(M, 7, generator=g), 1).to(dev),
+            (torch.rand(M, generator=g) * 2 - 1).to(dev), (torch.rand(M, generator=g) * 2 - 1).to(dev))
+    idx = torch.randperm(M, generator=g).to(dev)
+
+    def step_fn(heads, outputs, kind):
+        torch.manual_seed(0)
+        model = ConnectFourNet(ModelConfig(1, 32, 4, 2)).to(dev).train()
+        opt = HipAdam(model.parameters(), lr=2e-3, weight_decay=4e-4)
+        if kind == "graph":
+            graphed = GraphedTrainStep(model, opt, heads, M, data, outputs_path=outputs)
+            return lambda: graphed.run(idx)
+        return lambda: train_step(model, opt, tuple(t[idx] for t in data), heads, "torch", outputs)
+
+    fns = {f"heads={heads}/outputs={outputs}/{kind}": step_fn(heads, outputs, kind)
+           for kind in ("graph", "eager_hip_adam") for heads in ("torch", "bf16") for outputs in ("torch", "hip")}
+    step = alternating(fns, launches=5)
+    for v in step.values():
+        v["ms"] = v["us"] * 1e-3
+    res["step"] = dict(step, batch=M, model=[1, 32, 4, 2])
+    return res
+
+
 def generation(max_epochs: int, heads: str, graph: bool = False):
     from c4a0_amd import training as T
     from c4a0_amd.nn import ModelConfig
@@ -428,8 +517,20 @@ def main():
     ap.add_argument("--bf16", action="store_true", help='the heads="bf16" leg alone -> profiles/train_rate_bf16.json')
     ap.add_argument("--graph", action="store_true", help="the graphed-step leg alone -> profiles/train_rate_graph.json")
     ap.add_argument("--tower", action="store_true", help='the tower="hip" leg alone -> profiles/train_rate_tower.json')
+    ap.add_argument("--outputs", action="store_true", help='the outputs="hip" leg alone -> profiles/train_rate_outputs.json')
     a = ap.parse_args()
     out_path, max_epochs = a.out, a.max_epochs
+    if a.outputs:
+        if out_path == ap.get_default("out"):
+            out_path = os.path.join(ROOT, "profiles", "train_rate_outputs.json")
+        res = {"device": torch.cuda.get_device_name(0)}
+        res.update(outputs_leg())
+        print(json.dumps(res, indent=1), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        return
     if a.tower:
         if out_path == ap.get_default("out"):
             out_path = os.path.join(ROOT, "profiles", "train_rate_tower.json")
